@@ -1,6 +1,7 @@
 """bench.py — rays/sec of the NeRF hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|bf16_f8|fp32] [--mode train|render|eval]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -77,6 +78,10 @@ def parse():
                     help="N>1 graphed step: 1 = ONE graph with the hook-issued all-reduce(s) inside (the default since round 6; falls back to "
                          "two graphs, agreed across the ranks, when a collective cannot be captured), 0 = two graphs with the collectives "
                          "issued eagerly in between")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB "
+                         "in all): train mode the step's loss and PSNR and both models' parameters after its Adam update; render / eval "
+                         "mode the arrays render_rays / the image render returns")
     ap.add_argument("--grad-sync-form", default=None, choices=["merged", "per_model"],
                     help="N>1: merged (default) = the one-rank launches + ONE all-reduce of the step's joint gradient buffer; per_model = "
                          "the two models' backwards one after the other, the fine model's all-reduce under the coarse model's backward")
@@ -185,6 +190,31 @@ def timed_region(step_fn, warmup, steps, dist, device, series=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt_ = float(t.item())
     return dt_
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy in float32 (float64 stays float64).  Above DUMP_BYTES in all, every array of more
+    than one row keeps the same fixed, seeded sample of its rows (sorted), so two builds are compared on the same rows."""
+    import numpy as np
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+        host[k] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(x.nbytes for x in host.values())
+    if total > DUMP_BYTES:
+        frac = DUMP_BYTES / total
+        for k, x in host.items():
+            if x.ndim >= 1 and x.shape[0] > 1:
+                keep = max(1, int(x.shape[0] * frac))
+                host[k] = x[np.sort(np.random.default_rng(0).choice(x.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, x in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+    return sorted(host)
+
 
 def main():
     a = parse()
@@ -311,6 +341,13 @@ def main():
         return {k: v.cpu() for k, v in res.items()} if rank == 0 else res
 
     step = train_step if a.mode == "train" else (eval_step if a.mode == "eval" else render_step)
+    last = {}
+    if a.dump_outputs:                                       # keep what each step returns: the last timed one is dumped
+        step_ = step
+
+        def step():
+            last["out"] = step_()
+            return last["out"]
 
     series = [] if a.series else None
 
@@ -340,6 +377,17 @@ def main():
     if series is not None and rank == 0:
         print("[bench] per-step ms of the timed steps: %s" % json.dumps(series), file=sys.stderr, flush=True)
         series = None
+    if a.dump_outputs and rank == 0:
+        # the step's own outputs are overwritten by the next replay (and the models by the next step): taken before anything else runs
+        out_ = last["out"]
+        if a.mode == "train":
+            dump = {"loss": out_["loss"], "train_psnr": out_["progress_bar"]["train_psnr"]}
+            for tag, m in zip(("coarse", "fine"), models):
+                dump.update({"%s.%s" % (tag, n): p for n, p in m.named_parameters()})
+        else:
+            dump = dict(out_)
+        names = dump_outputs(a.dump_outputs, dump)
+        print("[bench] wrote %d arrays of the last timed step to %s" % (len(names), a.dump_outputs), file=sys.stderr, flush=True)
 
     if rank == 0:
         extra = {}

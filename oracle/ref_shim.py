@@ -6,9 +6,8 @@ thing missing in this image is the un-vendored `torchsearchsorted` submodule
 site `models/rendering.py:42` with side='right'); we inject a stand-in with
 numpy `searchsorted(side=...)` row-wise semantics built on `torch.searchsorted`.
 
-This module is used ONLY by `oracle/make_golden.py` (to mint fixtures) and by
-`tests/test_oracle_vs_reference.py` (skipped when /root/reference is absent, as
-on the GPU box).  Nothing in the product path imports it.
+This module is used ONLY by the `oracle/make_*.py` scripts (to mint fixtures) and by
+`tests/tools/dropin_probe.py` (by hand).  Nothing in the product path or the test suite imports it.
 """
 import importlib.util
 import os

@@ -104,3 +104,48 @@ def test_workload_c3_is_a_main_step_of_its_own():
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert "configs[3]" in d["config"]["workload"] and d["config"]["N_importance"] == 64 and d["ms_per_step"] > 0
     assert len(d["roofline_kernels"]) == 4
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs' writer: one DIR/<name>.npy per array, float64 kept, everything else float32; above the byte budget every
+    array of more than one row keeps the same seeded sample of rows, identical from call to call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"a": torch.arange(12, dtype=torch.float32).reshape(4, 3), "b": torch.ones(5, dtype=torch.float64),
+              "c": torch.tensor(2.5, dtype=torch.bfloat16), "coarse.sigma.weight": torch.arange(6, dtype=torch.int32)}
+    assert bench.dump_outputs(str(tmp_path / "d"), arrays) == sorted(arrays)
+    for k, v in arrays.items():
+        x = np.load(str(tmp_path / "d" / (k + ".npy")))
+        assert x.dtype == (np.float64 if k == "b" else np.float32) and np.array_equal(x, v.float().numpy())
+    big = {"x": torch.arange(4000, dtype=torch.float32).reshape(1000, 4), "s": torch.tensor(1.0)}
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    bench.dump_outputs(str(tmp_path / "e"), big)
+    bench.dump_outputs(str(tmp_path / "f"), big)
+    x, y = np.load(str(tmp_path / "e" / "x.npy")), np.load(str(tmp_path / "f" / "x.npy"))
+    assert x.nbytes <= 4000 and x.shape[1] == 4 and np.array_equal(x, y) and np.all(np.diff(x[:, 0]) > 0)
+    assert np.load(str(tmp_path / "e" / "s.npy")) == 1.0
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the loss, the PSNR and both models' parameters after the last timed step; the same arguments give the
+    same inputs, hence the same outputs, from run to run."""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "7", "--warmup", "2", "--settle", "0", "--no-extras", "--no-pmc", "--no-cpu-baseline"]
+    outs = []
+    for tag in ("a", "b"):
+        r = _run(common + ["--dump-outputs", str(tmp_path / tag)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 7 and d["ms_per_step"] > 0
+        names = sorted(f[:-4] for f in os.listdir(str(tmp_path / tag)))
+        outs.append({n: np.load(str(tmp_path / tag / (n + ".npy"))) for n in names})
+    a, b = outs
+    assert sorted(a) == sorted(b) and "loss" in a and "train_psnr" in a and len(a) == 2 + 2 * 24
+    assert a["coarse.xyz_encoding_1.0.weight"].shape == (256, 63) and a["fine.rgb.0.bias"].shape == (3,)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for n in a:
+        assert np.allclose(a[n], b[n], rtol=1e-5, atol=1e-7), (n, np.abs(a[n] - b[n]).max())

@@ -1,7 +1,6 @@
 """Host-side writers of the eval loop (N3): PFM byte-identical to the reference's datasets/depth_utils.py `save_pfm`
-(executed from /root/reference when present, and against a committed fixture everywhere), PNG round trip, depth bytes."""
+(against committed fixtures minted from the reference), PNG round trip, depth bytes."""
 import hashlib
-import importlib.util
 import os
 
 import numpy as np
@@ -9,7 +8,7 @@ import pytest
 
 from nerf_pl_amd import imageio_min as io
 
-REF_DU = "/root/reference/datasets/depth_utils.py"
+REF_CHECKS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_checks.npz")
 
 
 def _depth(h=37, w=53, seed=0):
@@ -27,8 +26,8 @@ def test_pfm_roundtrip_and_fixture(tmp_path):
     assert np.frombuffer(raw[-53 * 4:], dtype="<f4").tolist() == d[0].tolist()
     back, scale = io.read_pfm(p)
     assert scale == 1.0 and back.dtype == np.float32 and np.array_equal(back, d)
-    # fixture: sha256 of the file the REFERENCE's save_pfm (datasets/depth_utils.py:43-69) writes for this array, minted in
-    # the build container (test_pfm_bytes_identical_to_reference re-checks it there against the live reference)
+    # fixture: sha256 of the file the REFERENCE's save_pfm (datasets/depth_utils.py:43-69) writes for this array
+    # (test_pfm_bytes_identical_to_reference holds the bytes themselves)
     assert hashlib.sha256(raw).hexdigest() == "5426d477e73895a38eaf24cadd04f5c356eb02c4eea34c4f99556d11ef3c5969"
     col = np.stack([d, d * 0.5, d * 0.25], -1)
     io.save_pfm(p, col, scale=2)
@@ -38,19 +37,17 @@ def test_pfm_roundtrip_and_fixture(tmp_path):
         io.save_pfm(p, d.astype(np.float64))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DU), reason="reference tree not present")
 def test_pfm_bytes_identical_to_reference(tmp_path):
-    spec = importlib.util.spec_from_file_location("ref_depth_utils", REF_DU)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    for arr in (_depth(), _depth(8, 8, 3), np.stack([_depth(5, 7, 1)] * 3, -1), _depth(4, 6, 2)[..., None]):
-        a, b = str(tmp_path / "a.pfm"), str(tmp_path / "b.pfm")
-        ref.save_pfm(a, arr)
+    """The bytes the reference's save_pfm writes for each array, and what its read_pfm reads back from them
+    (tests/golden/reference_checks.npz, minted by oracle/make_golden_checks.py)."""
+    z = np.load(REF_CHECKS, allow_pickle=False)
+    arrs = (_depth(), _depth(8, 8, 3), np.stack([_depth(5, 7, 1)] * 3, -1), _depth(4, 6, 2)[..., None])
+    for i, arr in enumerate(arrs):
+        b = str(tmp_path / "b.pfm")
         io.save_pfm(b, arr)
-        assert open(a, "rb").read() == open(b, "rb").read()
-        ra, sa = ref.read_pfm(a)
+        assert open(b, "rb").read() == z["pfm%d_bytes" % i].tobytes()
         rb, sb = io.read_pfm(b)
-        assert sa == sb and np.array_equal(ra, rb)
+        assert float(z["pfm%d_scale" % i]) == sb and np.array_equal(z["pfm%d_read" % i], rb)
 
 
 def test_png_roundtrip(tmp_path):

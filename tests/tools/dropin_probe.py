@@ -1,6 +1,11 @@
-"""Runs in a SUBPROCESS (tests/test_dropin_reference_scripts.py): imports the REAL /root/reference/train.py and eval.py with
-the hot-path modules replaced by `nerf_pl_amd.install()` and the out-of-scope dependencies that this image lacks
-(pytorch_lightning 0.7.5, kornia, torchvision, cv2, imageio, the dataset loaders) stubbed, and prints a JSON report."""
+"""Drop-in proof, by hand where a reference tree is at hand (NERF_PL_REFERENCE, see oracle/ref_shim.py):
+
+    NERF_PL_REFERENCE=<reference tree> python tests/tools/dropin_probe.py
+
+imports the reference's REAL train.py and eval.py with the hot-path modules replaced by `nerf_pl_amd.install()` and the
+out-of-scope dependencies (pytorch_lightning 0.7.5, kornia, torchvision, cv2, imageio, the dataset loaders) stubbed, prints a
+JSON report and checks it (exit status 1 on a failed check).  Run it in a process of its own: the reference's top-level module
+names (`utils`, `datasets`, `metrics`, `eval`, ...) would shadow installed packages."""
 import importlib.util
 import inspect
 import json
@@ -8,9 +13,10 @@ import os
 import sys
 import types
 
-REF = "/root/reference"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+from oracle.ref_shim import REFERENCE_ROOT as REF  # noqa: E402
+
 sys.path.insert(1, REF)
 
 import torch  # noqa: E402
@@ -125,3 +131,32 @@ if report["gpu"]:
     finally:
         dist.destroy_process_group()
 print("DROPIN_REPORT " + json.dumps(report))
+
+
+def check(rep):
+    for k in ("train.render_rays_is_ours", "eval.render_rays_is_ours", "train.Embedding_is_ours", "system.models_are_ours",
+              "system.embeddings_are_ours", "forward_calls_render_rays", "load_ckpt_roundtrip"):
+        assert rep[k] is True, (k, rep)
+    assert rep["embedding_channels"] == [63, 27]
+    assert rep["state_dict_keys"] == 48                       # 2 models x 12 layers x (weight, bias)
+    # train.py:55-64 passes these ten positionally
+    assert rep["render_rays_signature"][:10] == ["models", "embeddings", "rays", "N_samples", "use_disp", "perturb", "noise_std",
+                                                  "N_importance", "chunk", "white_back"]
+    assert rep["render_rays_signature"][10] == "test_time"    # eval.py:69-79 passes it by keyword
+    assert rep["optimizer"] == "Adam" and rep["optimizer_params"] == 2 * 595844 and rep["scheduler"] == "MultiStepLR"
+    assert rep["eval_batched_inference_args"] == ["models", "embeddings", "rays", "N_samples", "N_importance", "use_disp", "chunk",
+                                                  "white_back"]
+    assert rep["loss"] == "MSELoss"
+    if rep.get("gpu"):         # with an MI355X as well: the reference's own training_step ran on our kernels
+        ls = rep["training_step_losses"]
+        assert rep["training_step_keys"] == ["log", "loss", "progress_bar"] and rep["training_step_grads_finite"]
+        assert all(l == l and l < 10 for l in ls) and min(ls[2:]) < ls[0], ls
+        assert rep["ddp_world1_loss"] == rep["ddp_world1_loss"]
+
+
+try:
+    check(report)
+except AssertionError as e:
+    print("DROPIN_CHECK_FAILED %s" % (e,), file=sys.stderr)
+    sys.exit(1)
+print("DROPIN_CHECK ok")
