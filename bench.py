@@ -1,7 +1,7 @@
 """bench.py — rays/sec of the NeRF hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|bf16_f8|fp32] [--mode train|render|eval]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,6 +14,11 @@ contract: render_rays forward (coarse + fine, 256 MLP evaluations per ray) -> MS
 backward through compositing and both MLPs -> [N>1: RCCL all-reduce of the gradients] -> Adam step.
 `--mode render` times the forward `render_rays` alone.  Ray batches shard across ranks (weak scaling:
 1024 rays per GPU, like the reference's DDP).  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline alone: set-up, the steps of the protocol below, the dump of --dump-outputs and the line.
+`--full` adds, after the headline's timed steps, everything else the benchmark measures: the forward-only and configs[4] eval
+rates, the north-star kernel and the step's per-kernel roofline, HBM counters from rocprofv3 --pmc passes, the fp8-dW, configs[1]
+and configs[3] side steps and the CPU baseline (`--no-extras`, `--no-pmc` and `--no-cpu-baseline` leave parts of it out).
 """
 import argparse
 import json
@@ -44,7 +49,7 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "bf16_f8", "fp32"],
                     help="bf16 (default; the arithmetic BASELINE.json configs[2] names): bf16 MFMA everywhere, saved tensors in bf16; "
                          "bf16_f8: the same forward + dX chain, saved activations/dY stored as block-scaled 8-bit floats and the dW GEMM on "
-                         "the MX-scaled fp8 MFMA (reported beside the headline as f8_dw_ms_per_step); fp32: exact-fp32 MFMA (parity)")
+                         "the MX-scaled fp8 MFMA (--full reports it beside the headline as f8_dw_ms_per_step); fp32: exact-fp32 MFMA (parity)")
     ap.add_argument("--mode", default="train", choices=["train", "render", "eval"])
     ap.add_argument("--image-rays", type=int, default=640000, help="--mode eval: rays per image (800x800), sharded over ranks")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3"],
@@ -55,9 +60,12 @@ def parse():
     ap.add_argument("--rays", type=int, default=1024)
     ap.add_argument("--n-samples", type=int, default=64)
     ap.add_argument("--n-importance", type=int, default=None, help="default 128 (workload c2) / 64 (c3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures (forward-only and eval rates, north-star kernel, "
+                         "per-kernel roofline, HBM counters, fp8-dW / configs[1] / configs[3] side steps, CPU baseline); off: the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="issue the training step eagerly instead of replaying a hipGraph")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU seconds the CPU baseline may spend")
     ap.add_argument("--fixed-batch", action="store_true", help="replay one resident batch instead of drawing a fresh one per step")
     ap.add_argument("--modular-step", action="store_true",
                     help="training_step through the modular autograd graph (render_rays -> MSELoss) instead of the fused node (A/B)")
@@ -66,11 +74,11 @@ def parse():
                          "SLOWER per step in six same-call pairs on four boxes, so off by default)")
     ap.add_argument("--no-fuse-adam", action="store_true", help="(the default since round 3; accepted for older command lines)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="train mode: skip the side measurements (eval / render / fp8-dW variant / configs[1] and configs[3] steps / PMC passes)")
+                    help="--full, train mode: skip the side measurements (eval image / fp8-dW variant / configs[1] and configs[3] steps / PMC passes)")
     ap.add_argument("--settle", type=int, default=None,
                     help="untimed replays between the capture and the W warm-up steps (device clocks; default by mode, 0 = none)")
     ap.add_argument("--series", action="store_true", help="diagnosis: per-step durations of the timed steps (events between the steps) on stderr")
-    ap.add_argument("--no-pmc", action="store_true", help="do not take HBM counters in-run (rocprofv3 --pmc passes of this build's kernels)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not take HBM counters in-run (rocprofv3 --pmc passes of this build's kernels)")
     ap.add_argument("--pmc-launch", action="store_true", help=argparse.SUPPRESS)   # child mode of the PMC passes: launch the kernels, print nothing
     ap.add_argument("--force-dist", action="store_true",
                     help="N=1: initialise the RCCL process group and route gradients through GradSync anyway (A/B of the N>1 step)")
@@ -391,93 +399,7 @@ def main():
 
     if rank == 0:
         extra = {}
-        from bench_extras import event_time, kernel_table, load_traffic_db
-        traffic_db = load_traffic_db(extra)
-        if a.mode == "train" and world == 1 and not a.no_extras and not a.no_pmc and a.dtype != "fp32":
-            from bench_extras import pmc_collect
-            live = pmc_collect(a, extra)                     # this box's own counters replace the stamped file's
-            if live:
-                traffic_db = dict(traffic_db, **live)
-        if a.mode == "train":                                  # forward-only rate of the same workload
-            for _ in range(5):
-                render_step()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(30):
-                render_step()
-            torch.cuda.synchronize()
-            t_render = (time.perf_counter() - t1) / 30
-            extra["render_fwd_rays_per_s_per_gpu"] = round(B / t_render, 1)
-            # train-mode forward = full coarse + full fine network: FLOP_PER_POINT_FULL x (2S + N) points per ray
-            extra["render_fwd_frac_mfma"] = round(FLOP_PER_POINT_FULL * B * (2 * S + N) / t_render / 1e12 / PEAK_TFLOPS[a.dtype], 4)
-            if world == 1 and not a.no_extras:
-                # BASELINE configs[4] inside the default run: full 800x800 images through eval.py's batched_inference contract
-                # (test_time, 32768-ray hipGraph chunks, pixels streamed to pinned host memory: D2H inside the timed region)
-                from nerf_pl_amd.inference import GraphRenderer
-                e_rays = synth_rays(77, a.image_rays).to(dev)
-                gr = GraphRenderer(models, emb, S, N, False, True)
-                gr.render_to_host(e_rays, keys=("rgb_fine", "depth_fine"))
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                for _ in range(3):
-                    gr.render_to_host(e_rays, keys=("rgb_fine", "depth_fine"))
-                torch.cuda.synchronize()
-                t_img = (time.perf_counter() - t1) / 3
-                extra["eval_ms_per_image"] = round(t_img * 1e3, 2)
-                extra["eval_rays_per_s"] = round(a.image_rays / t_img, 1)
-                extra["eval_frac_mfma"] = round(FLOP_PER_RAY_EVAL * a.image_rays / t_img / 1e12 / PEAK_TFLOPS[a.dtype], 4)
-                extra["eval_note"] = ("configs[4]: %d-ray image, 32768-ray hipGraph chunks x (%d+%d) samples, test_time (sigma-only coarse "
-                                      "pass), D2H of rgb+depth included; 3 images after 1 warm-up" % (a.image_rays, S, N))
-                del gr, e_rays
-
-        # ---- the north-star kernel: fine-pass fused MLP forward, inference variant (B x (S+N) points) ----
-        with torch.no_grad():
-            z = ops.sample_coarse_z(rays, S, False, 0.0)
-            zf = ops.fine_z(z, torch.rand(B, S, device=dev), N)
-            pk = models[1].packed_weights()                     # pack once: the events bracket the MLP kernel alone
-            avg_us, min_us = event_time(lambda: ops.mlp_fwd_rays(rays, zf, pk, False, a.dtype), 30, warm=5)
-        flops = FLOP_PER_POINT_FULL * B * (S + N)
-        ach = flops / avg_us / 1e6
-        ns = {"bound": "mfma", "kernel": "mlp_fwd_kernel<%s,rays,full> (inference) %dx%d points" % (a.dtype, B, S + N),
-              "achieved": round(ach, 2), "peak": PEAK_TFLOPS[a.dtype], "unit": "TFLOP/s",
-              "frac": round(ach / PEAK_TFLOPS[a.dtype], 4),
-              "traffic": traffic_db.get("mlp_fwd_kernel|%s|%d" % (a.dtype, B * (S + N)), {}).get("hbm_bytes_per_launch"),
-              "avg_launch_us": round(avg_us, 2), "min_launch_us": round(min_us, 2),
-              # `frac` prices the reference's GEMMs (1,186,816 FLOP / point); the kernel executes 1,055,744 of them per point:
-              # xyz_encoding_final has no activation and is folded into the dir layer (csrc/mlp_layout.h kLayers)
-              "frac_executed": round(FLOP_PER_POINT_FULL_EXECUTED * B * (S + N) / avg_us / 1e6 / PEAK_TFLOPS[a.dtype], 4)}
-        if a.dtype != "fp32":
-            # informational: what this chip sustains at all under back-to-back bf16 MFMAs (it is power-limited: the shader
-            # clock settles at 1.45-1.83 GHz), measured by tools/probes/probe_mfma_rate.hip -> profiles/archive/r02_probe_mfma_rate.txt
-            ns["measured_ceiling"] = {"bare_mfma_frac_of_peak": [0.61, 0.66], "this_instruction_mix_frac_of_peak": [0.57, 0.59],
-                                      "source": "profiles/archive/r02_probe_mfma_rate.txt"}
         if a.mode == "train":
-            # ---- the kernels the TIMED step runs, one entry each; `roofline` = the one that takes the most time ----
-            table, mix_us = kernel_table(models, rays, S, N, a.dtype, dev, traffic_db, merged=(system.fused_train_step and (grad_sync is None or grad_sync.form == "merged")))
-            dom = max(table, key=lambda r: r["in_step_launch_us"])
-            # The headline figure follows SURVEY 8(d): an MLP kernel is priced against the dense MFMA peak of its arithmetic with the
-            # ALGORITHMIC FLOPs of the GEMMs it performs.  The HBM view of the same launch (this design materialises activations
-            # and dY for the weight-gradient GEMM: bytes that 8(d)'s fused arithmetic intensity does not contain) rides beside it.
-            # Durations: the kernel's time INSIDE the step's kernel mix (`in_step_launch_us`: what the rocprofv3 trace of this command
-            # shows for it); the same launch repeated alone settles at its own clock and runs a few % faster (`alone_launch_us`).
-            us = dom["in_step_launch_us"]
-            gbs_, tf_ = dom["hbm_bytes"] / us / 1e3, dom["flops"] / us / 1e6
-            roof = {"bound": dom["bound"], "kernel": dom["kernel"],
-                    "achieved": round(gbs_ if dom["bound"] == "hbm" else tf_, 1),
-                    "peak": PEAK_HBM_GBS if dom["bound"] == "hbm" else dom["mfma_peak_tflops"],
-                    "unit": "GB/s" if dom["bound"] == "hbm" else "TFLOP/s",
-                    "frac": dom["frac_hbm_in_step"] if dom["bound"] == "hbm" else dom["frac_mfma_in_step"],
-                    "traffic": dom["traffic"], "avg_launch_us": us, "alone_launch_us": dom["avg_launch_us"],
-                    "frac_mfma": dom["frac_mfma_in_step"], "frac_hbm": dom["frac_hbm_in_step"], "limited_by": dom["limited_by"],
-                    "hbm_view": {"achieved": round(gbs_, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": dom["frac_hbm_in_step"],
-                                 "bytes": dom["hbm_bytes"], "bytes_are": dom["bytes_are"]}}
-            extra["roofline"] = roof
-            extra["roofline_kernels"] = table
-            extra["roofline_north_star"] = ns
-            # the step's MLP kernels replayed together in step order from one graph (<= ms_per_step * 1000) / summed from the
-            # kernel-alone entries (each at its own clock: may come out above or below the former, box dependent)
-            extra["mlp_kernels_us_per_step"] = mix_us
-            extra["mlp_kernels_us_alone_sum"] = round(sum(r["avg_launch_us"] for r in table), 1)
             # whole-step MFMA fraction: algorithmic FLOPs of the step (GEMMs only) over the step time
             step_flops = (FLOP_PER_POINT_FULL + FLOP_PER_POINT_DX + FLOP_PER_POINT_DW) * B * (2 * S + N)
             extra["step_frac_mfma"] = round(step_flops / (dt / a.steps) / 1e12 / PEAK_TFLOPS[a.dtype], 4)
@@ -489,12 +411,100 @@ def main():
                 from nerf_pl_amd.system import graph_node_count
                 # nodes of the replayed hipGraph = launches per step (hipGraphGetNodes on the captured graph)
                 extra["launches_per_step"] = graph_node_count(g_.graph)
-            extra["non_mlp_us"] = round(dt / a.steps * 1e6 - mix_us, 1)      # step - the six MLP kernels replayed together
-            if world == 1 and not a.no_extras:
-                from bench_extras import side_steps
-                extra.update(side_steps(a, hp, build_system, make_stepper, timed, dev))
-        else:
-            extra["roofline"] = ns
+        if a.full:                                             # everything else the benchmark measures, after the headline
+            from bench_extras import event_time, kernel_table, load_traffic_db
+            traffic_db = load_traffic_db(extra)
+            if a.mode == "train" and world == 1 and not a.no_extras and not a.no_pmc and a.dtype != "fp32":
+                from bench_extras import pmc_collect
+                live = pmc_collect(a, extra)                     # this box's own counters replace the stamped file's
+                if live:
+                    traffic_db = dict(traffic_db, **live)
+            if a.mode == "train":                                  # forward-only rate of the same workload
+                for _ in range(5):
+                    render_step()
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(30):
+                    render_step()
+                torch.cuda.synchronize()
+                t_render = (time.perf_counter() - t1) / 30
+                extra["render_fwd_rays_per_s_per_gpu"] = round(B / t_render, 1)
+                # train-mode forward = full coarse + full fine network: FLOP_PER_POINT_FULL x (2S + N) points per ray
+                extra["render_fwd_frac_mfma"] = round(FLOP_PER_POINT_FULL * B * (2 * S + N) / t_render / 1e12 / PEAK_TFLOPS[a.dtype], 4)
+                if world == 1 and not a.no_extras:
+                    # BASELINE configs[4] inside the --full run: full 800x800 images through eval.py's batched_inference contract
+                    # (test_time, 32768-ray hipGraph chunks, pixels streamed to pinned host memory: D2H inside the timed region)
+                    from nerf_pl_amd.inference import GraphRenderer
+                    e_rays = synth_rays(77, a.image_rays).to(dev)
+                    gr = GraphRenderer(models, emb, S, N, False, True)
+                    gr.render_to_host(e_rays, keys=("rgb_fine", "depth_fine"))
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    for _ in range(3):
+                        gr.render_to_host(e_rays, keys=("rgb_fine", "depth_fine"))
+                    torch.cuda.synchronize()
+                    t_img = (time.perf_counter() - t1) / 3
+                    extra["eval_ms_per_image"] = round(t_img * 1e3, 2)
+                    extra["eval_rays_per_s"] = round(a.image_rays / t_img, 1)
+                    extra["eval_frac_mfma"] = round(FLOP_PER_RAY_EVAL * a.image_rays / t_img / 1e12 / PEAK_TFLOPS[a.dtype], 4)
+                    extra["eval_note"] = ("configs[4]: %d-ray image, 32768-ray hipGraph chunks x (%d+%d) samples, test_time (sigma-only coarse "
+                                          "pass), D2H of rgb+depth included; 3 images after 1 warm-up" % (a.image_rays, S, N))
+                    del gr, e_rays
+
+            # ---- the north-star kernel: fine-pass fused MLP forward, inference variant (B x (S+N) points) ----
+            with torch.no_grad():
+                z = ops.sample_coarse_z(rays, S, False, 0.0)
+                zf = ops.fine_z(z, torch.rand(B, S, device=dev), N)
+                pk = models[1].packed_weights()                     # pack once: the events bracket the MLP kernel alone
+                avg_us, min_us = event_time(lambda: ops.mlp_fwd_rays(rays, zf, pk, False, a.dtype), 30, warm=5)
+            flops = FLOP_PER_POINT_FULL * B * (S + N)
+            ach = flops / avg_us / 1e6
+            ns = {"bound": "mfma", "kernel": "mlp_fwd_kernel<%s,rays,full> (inference) %dx%d points" % (a.dtype, B, S + N),
+                  "achieved": round(ach, 2), "peak": PEAK_TFLOPS[a.dtype], "unit": "TFLOP/s",
+                  "frac": round(ach / PEAK_TFLOPS[a.dtype], 4),
+                  "traffic": traffic_db.get("mlp_fwd_kernel|%s|%d" % (a.dtype, B * (S + N)), {}).get("hbm_bytes_per_launch"),
+                  "avg_launch_us": round(avg_us, 2), "min_launch_us": round(min_us, 2),
+                  # `frac` prices the reference's GEMMs (1,186,816 FLOP / point); the kernel executes 1,055,744 of them per point:
+                  # xyz_encoding_final has no activation and is folded into the dir layer (csrc/mlp_layout.h kLayers)
+                  "frac_executed": round(FLOP_PER_POINT_FULL_EXECUTED * B * (S + N) / avg_us / 1e6 / PEAK_TFLOPS[a.dtype], 4)}
+            if a.dtype != "fp32":
+                # informational: what this chip sustains at all under back-to-back bf16 MFMAs (it is power-limited: the shader
+                # clock settles at 1.45-1.83 GHz), measured by tools/probes/probe_mfma_rate.hip -> profiles/archive/r02_probe_mfma_rate.txt
+                ns["measured_ceiling"] = {"bare_mfma_frac_of_peak": [0.61, 0.66], "this_instruction_mix_frac_of_peak": [0.57, 0.59],
+                                          "source": "profiles/archive/r02_probe_mfma_rate.txt"}
+            if a.mode == "train":
+                # ---- the kernels the TIMED step runs, one entry each; `roofline` = the one that takes the most time ----
+                table, mix_us = kernel_table(models, rays, S, N, a.dtype, dev, traffic_db, merged=(system.fused_train_step and (grad_sync is None or grad_sync.form == "merged")))
+                dom = max(table, key=lambda r: r["in_step_launch_us"])
+                # The headline figure follows SURVEY 8(d): an MLP kernel is priced against the dense MFMA peak of its arithmetic with the
+                # ALGORITHMIC FLOPs of the GEMMs it performs.  The HBM view of the same launch (this design materialises activations
+                # and dY for the weight-gradient GEMM: bytes that 8(d)'s fused arithmetic intensity does not contain) rides beside it.
+                # Durations: the kernel's time INSIDE the step's kernel mix (`in_step_launch_us`: what the rocprofv3 trace of this command
+                # shows for it); the same launch repeated alone settles at its own clock and runs a few % faster (`alone_launch_us`).
+                us = dom["in_step_launch_us"]
+                gbs_, tf_ = dom["hbm_bytes"] / us / 1e3, dom["flops"] / us / 1e6
+                roof = {"bound": dom["bound"], "kernel": dom["kernel"],
+                        "achieved": round(gbs_ if dom["bound"] == "hbm" else tf_, 1),
+                        "peak": PEAK_HBM_GBS if dom["bound"] == "hbm" else dom["mfma_peak_tflops"],
+                        "unit": "GB/s" if dom["bound"] == "hbm" else "TFLOP/s",
+                        "frac": dom["frac_hbm_in_step"] if dom["bound"] == "hbm" else dom["frac_mfma_in_step"],
+                        "traffic": dom["traffic"], "avg_launch_us": us, "alone_launch_us": dom["avg_launch_us"],
+                        "frac_mfma": dom["frac_mfma_in_step"], "frac_hbm": dom["frac_hbm_in_step"], "limited_by": dom["limited_by"],
+                        "hbm_view": {"achieved": round(gbs_, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": dom["frac_hbm_in_step"],
+                                     "bytes": dom["hbm_bytes"], "bytes_are": dom["bytes_are"]}}
+                extra["roofline"] = roof
+                extra["roofline_kernels"] = table
+                extra["roofline_north_star"] = ns
+                # the step's MLP kernels replayed together in step order from one graph (<= ms_per_step * 1000) / summed from the
+                # kernel-alone entries (each at its own clock: may come out above or below the former, box dependent)
+                extra["mlp_kernels_us_per_step"] = mix_us
+                extra["mlp_kernels_us_alone_sum"] = round(sum(r["avg_launch_us"] for r in table), 1)
+                extra["non_mlp_us"] = round(dt / a.steps * 1e6 - mix_us, 1)      # step - the six MLP kernels replayed together
+                if world == 1 and not a.no_extras:
+                    from bench_extras import side_steps
+                    extra.update(side_steps(a, hp, build_system, make_stepper, timed, dev))
+            else:
+                extra["roofline"] = ns
 
         total_rays = (a.image_rays if a.mode == "eval" else world * B) * a.steps
         arith = DTYPE_LABEL[a.dtype]
@@ -562,7 +572,7 @@ def main():
                                    "warm-up as cold_start_ms_per_step; rounds 1-3 (protocol 1) counted the build calls as warm-up steps"}
         out.update(extra)
         out["parity"] = PARITY
-        if not a.no_cpu_baseline and world == 1:                # reported baseline: rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:     # reported baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(B, S, N, a.cpu_seconds, a.mode == "train")
         real_stdout.write(json.dumps(out) + "\n")
         real_stdout.flush()

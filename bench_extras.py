@@ -1,4 +1,4 @@
-"""bench_extras.py — the side measurements of bench.py's default line (split out of bench.py in round 6, no behaviour change).
+"""bench_extras.py — the side measurements of bench.py's --full line (split out of bench.py in round 6, no behaviour change).
 
 Nothing here is inside the contract's timed region (that is bench.py: `timed_region`).  What lives here:
   * `pmc_launch` / `pmc_collect` / `load_traffic_db` — HBM counters of THIS run's kernels (rocprofv3 --pmc, separate FETCH_SIZE /
@@ -347,7 +347,7 @@ def kernel_table(models, rays, S, N, dtype, dev, traffic_db, merged):
 
 
 def side_steps(a, hp, build_system, make_stepper, timed, dev):
-    """Extras of the default line, measured AFTER the headline's timed region: the fp8-dW variant of the same step (its own
+    """Extras of the --full line, measured AFTER the headline's timed region: the fp8-dW variant of the same step (its own
     process: a dedicated run, not a second system squeezed into this one), BASELINE configs[1] (fp32, 64+64) and configs[3]
     (NDC rays, noise_std=1, black background, 64+64) training steps."""
     import subprocess
@@ -358,7 +358,7 @@ def side_steps(a, hp, build_system, make_stepper, timed, dev):
     ex = {}
     step_flops_pt = FLOP_PER_POINT_FULL + FLOP_PER_POINT_DX + FLOP_PER_POINT_DW
     if a.dtype == "bf16":
-        cmd = [sys.executable, BENCH_PY, "--dtype", "bf16_f8", "--steps", "15", "--warmup", "6", "--no-extras",
+        cmd = [sys.executable, BENCH_PY, "--dtype", "bf16_f8", "--steps", "15", "--warmup", "6", "--full", "--no-extras",
                "--no-cpu-baseline", "--rays", str(B), "--n-samples", str(S), "--n-importance", str(N)]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=150)

@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -57,11 +58,11 @@ def test_torchrun_world1_rccl_path_agrees_with_the_plain_run():
 
 @pytest.mark.gpu
 def test_driver_command_line_shape():
-    """The driver's own command: ONE JSON line whose headline, `literal_contract`, `protocol`, `roofline` and `cpu_baseline` objects are
-    self-consistent (round 6, protocol 3: build -> exactly W untimed + K timed steps = `literal_contract` -> settle replays -> W + K again
-    = `value`; every MLP kernel carries its duration inside the step's kernel mix; the CPU baseline states the node's core count AND
-    the threads it used)."""
-    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extras", "--no-pmc", "--cpu-seconds", "2"])
+    """The driver's own command with `--full`: ONE JSON line whose headline, `literal_contract`, `protocol`, `roofline` and `cpu_baseline`
+    objects are self-consistent (round 6, protocol 3: build -> exactly W untimed + K timed steps = `literal_contract` -> settle replays ->
+    W + K again = `value`; every MLP kernel carries its duration inside the step's kernel mix; the CPU baseline states the node's core
+    count AND the threads it used)."""
+    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-extras", "--no-pmc", "--cpu-seconds", "2"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -89,6 +90,27 @@ def test_driver_command_line_shape():
 
 
 @pytest.mark.gpu
+def test_plain_run_measures_the_headline_alone():
+    """Without `--full` the line carries the headline and what follows from its own steps (`literal_contract`, `protocol`, the step's
+    MFMA fraction and launch count); none of the side measurements runs, so the run spends seconds, not minutes, outside its steps."""
+    t0 = time.perf_counter()
+    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and "full training step" in d["metric"] and "configs[2]" in d["config"]["workload"]
+    assert abs(d["value"] - 1024 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    assert d["protocol"]["settle_replays_since_build"] == 150 and d["literal_contract"]["steps"] == 20 and d["launches_per_step"] == 7
+    side = {"roofline", "roofline_kernels", "roofline_north_star", "mlp_kernels_us_per_step", "traffic_note", "cpu_baseline",
+            "render_fwd_rays_per_s_per_gpu", "eval_ms_per_image", "f8_dw_ms_per_step", "fp32_c1_ms_per_step", "ndc_c3_ms_per_step"}
+    assert not side & set(d), sorted(side & set(d))
+    assert wall - 25 * d["ms_per_step"] * 1e-3 < 60, wall
+
+
+@pytest.mark.gpu
 def test_settle_0_reports_the_literal_contract_as_the_value():
     r = _run(["--gpus", "1", "--steps", "10", "--warmup", "3", "--no-extras", "--no-pmc", "--no-cpu-baseline", "--settle", "0"])
     assert r.returncode == 0, r.stderr[-2000:]
@@ -99,7 +121,7 @@ def test_settle_0_reports_the_literal_contract_as_the_value():
 @pytest.mark.gpu
 def test_workload_c3_is_a_main_step_of_its_own():
     """configs[3] per GPU (NDC rays, noise_std 1, black background, 64 + 64) as the main step: what tools/ktrace_step.sh traces."""
-    r = _run(["--workload", "c3", "--steps", "10", "--warmup", "3", "--no-extras", "--no-pmc", "--no-cpu-baseline"])
+    r = _run(["--workload", "c3", "--steps", "10", "--warmup", "3", "--full", "--no-extras", "--no-pmc", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert "configs[3]" in d["config"]["workload"] and d["config"]["N_importance"] == 64 and d["ms_per_step"] > 0

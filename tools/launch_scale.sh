@@ -19,7 +19,7 @@ NGPU=$(python -c "import torch; print(torch.cuda.device_count())")
 RAN=""
 for N in 1 2 4 8; do
   if [ "$N" -gt "$NGPU" ]; then echo "[scale] only $NGPU GPU(s) visible: skipping N=$N"; continue; fi
-  python bench.py --gpus $N --steps 50 --warmup 10 --no-cpu-baseline "$@" > $OUT/n$N.json 2> $OUT/n$N.err || { echo "[scale] N=$N failed (rc $?)"; tail -5 $OUT/n$N.err; continue; }
+  python bench.py --gpus $N --steps 50 --warmup 10 --full --no-cpu-baseline "$@" > $OUT/n$N.json 2> $OUT/n$N.err || { echo "[scale] N=$N failed (rc $?)"; tail -5 $OUT/n$N.err; continue; }
   RAN="$RAN $N"
   if [ "$N" -gt 1 ]; then
     python bench.py --gpus $N --steps 50 --warmup 10 --no-cpu-baseline --no-extras --grad-sync-form per_model "$@" > $OUT/n${N}_per_model.json 2> $OUT/n${N}_per_model.err || echo "[scale] N=$N per_model failed"
