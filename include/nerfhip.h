@@ -467,6 +467,56 @@ int nerfhip_render_test_fwd(const nerfhip_render_args* args_host, int dtype, ner
  * finish in nerfhip_mse_psnr's own order).  Bit-identical to those launches.                                                 */
 int nerfhip_render_train_fwd(const nerfhip_render_args* args_host, int dtype, nerfhip_stream_t stream);
 
+/* ---- mesh extraction  (extract_color_mesh.py:144-285; nerf_pl_amd/mesh.py, DESIGN.md "Mesh extraction") -----------------
+ * Marching cubes on a dense float32 volume (n0,n1,n2), C order, every dimension >= 2, n0*n1*n2 < 2^31.  Bourke's tables: case
+ * bit i set where corner i is below `iso` (compared in fp64).  One vertex per crossed lattice edge (shared by every triangle on
+ * it) at a + t, t = (iso - f_a) / (f_b - f_a) in fp64 (0.5 when f_a == f_b), ordered by (owning lattice point in C order, edge
+ * axis); triangles ordered by (cell in C order, table order).  Deterministic.  Two calls on one workspace:
+ *   count  writes totals[0] = V, totals[1] = T (int64, DEVICE);
+ *   emit   the caller reads the totals, refuses V or T >= 2^31 (emit then writes nothing) and passes vertices (V,3) fp64 and
+ *          triangles (T,3) int32.                                                                                          */
+size_t nerfhip_marching_cubes_workspace_bytes(int64_t n0, int64_t n1, int64_t n2);   /* 0: unsupported shape */
+int nerfhip_marching_cubes_count(const float* volume, int64_t n0, int64_t n1, int64_t n2, double iso, void* workspace,
+                                 int64_t* totals, nerfhip_stream_t stream);
+int nerfhip_marching_cubes_emit(const float* volume, int64_t n0, int64_t n1, int64_t n2, double iso, void* workspace,
+                                const int64_t* totals, double* vertices, int32_t* triangles, nerfhip_stream_t stream);
+
+/* Largest edge-connected triangle cluster (open3d cluster_connected_triangles + argmax + remove_unreferenced_vertices).
+ * keys (3T) int64: (min << 32 | max) of every triangle's edges (t, 0-1), (t, 1-2), (t, 2-0) at 3t..3t+2.  The caller sorts them
+ * (sorted_keys, order = the permutation as int64) and calls largest_cluster, which writes totals[0] = kept triangles,
+ * totals[1] = kept vertices, totals[2] = nonzero on failure; then compact writes kept_vertex_ids (totals[1]) int64 (old ids,
+ * ascending) and kept_triangles (totals[0],3) int32 (surviving triangles in order, remapped).  Ties between clusters of equal
+ * size go to the one holding the lowest triangle id.  Every vertex id must lie in [0, V).                                  */
+int nerfhip_mesh_edge_keys(const int32_t* triangles, int64_t T, int64_t* keys, nerfhip_stream_t stream);
+size_t nerfhip_mesh_cluster_workspace_bytes(int64_t V, int64_t T);
+int nerfhip_mesh_largest_cluster(const int32_t* triangles, int64_t V, int64_t T, const int64_t* sorted_keys, const int64_t* order,
+                                 void* workspace, int64_t* totals, nerfhip_stream_t stream);
+int nerfhip_mesh_cluster_compact(const int32_t* triangles, int64_t V, int64_t T, void* workspace, int64_t* kept_vertex_ids,
+                                 int32_t* kept_triangles, nerfhip_stream_t stream);
+
+/* Vertex normals by open3d's rule: sum of unnormalised face cross products (v1-v0)x(v2-v0) in fp64 (atomic, so the last bits
+ * follow the summation order), normalised; zero-length -> (0,0,1).  vertices (V,3) float32 -> normals (V,3) fp64.           */
+int nerfhip_mesh_vertex_normals(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, double* normals,
+                                nerfhip_stream_t stream);
+/* extract_color_mesh.py:190-195: rays (V,8) = [v - d*near*near_t, d, near, far], d = float32(normal).                      */
+int nerfhip_mesh_normal_rays(const float* vertices, const double* normals, int64_t V, float near, float far, float near_t,
+                             float* rays, nerfhip_stream_t stream);
+/* One view of extract_color_mesh.py:223-264.  w2c_host: 12 HOST floats (top rows of the float32 inverse of the 4x4 c2w),
+ * origin_host: 3 HOST floats (the pose's last column).  Projection in fp64 with y, z negated, K = [[f,0,W/2],[0,f,H/2],[0,0,1]],
+ * depth = z + 1e-5, pixel = float32(xy / depth) clipped to [0,W-1] x [0,H-1]; image (H,W,3) uint8 sampled as cv2.remap
+ * INTER_LINEAR does (1/32 px positions, 15-bit weights).  Writes colors (V,4) uint8 (4th byte 0), depth (V) fp64 and the
+ * occlusion rays (V,8) = [camera centre, normalised direction, near, float32(depth)].                                    */
+int nerfhip_mesh_view_rays(const float* vertices, int64_t V, const float* w2c_host, const float* origin_host, float focal, int W,
+                           int H, const uint8_t* image, float near, uint8_t* colors, double* depth, float* rays,
+                           nerfhip_stream_t stream);
+/* accum (V,4) fp64 += [colour * w, w], w = 0.1 / depth + (opacity < occ_threshold), NaN opacity counted as 0.             */
+int nerfhip_mesh_color_accumulate(const uint8_t* colors, const double* depth, const float* opacity, int64_t V,
+                                  float occ_threshold, double* accum, nerfhip_stream_t stream);
+/* out (V,3) uint8 = trunc(accum[:, :3] / accum[:, 3])                                                                     */
+int nerfhip_mesh_color_finish(const double* accum, int64_t V, uint8_t* out, nerfhip_stream_t stream);
+/* out (n) uint8 = trunc(float32(rgb * 255)): the vertex-normal mode's colours (extract_color_mesh.py:279)                  */
+int nerfhip_mesh_rgb_to_u8(const float* rgb, int64_t n, uint8_t* out, nerfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

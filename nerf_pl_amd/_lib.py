@@ -103,6 +103,21 @@ SIGNATURES = {
     "nerfhip_linear_bwd_weight_workspace_bytes": [_i64, _int, _int],
     "nerfhip_linear_bwd_weight": [_c_void_p, _i64, _c_void_p, _i64, _int, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p,
                                   _i64, _int, _int, _int, _int, _c_void_p],
+    "nerfhip_marching_cubes_workspace_bytes": [_i64, _i64, _i64],
+    "nerfhip_marching_cubes_count": [_c_void_p, _i64, _i64, _i64, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_marching_cubes_emit": [_c_void_p, _i64, _i64, _i64, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                    _c_void_p],
+    "nerfhip_mesh_edge_keys": [_c_void_p, _i64, _c_void_p, _c_void_p],
+    "nerfhip_mesh_cluster_workspace_bytes": [_i64, _i64],
+    "nerfhip_mesh_largest_cluster": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_cluster_compact": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_vertex_normals": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "nerfhip_mesh_normal_rays": [_c_void_p, _c_void_p, _i64, _f32, _f32, _f32, _c_void_p, _c_void_p],
+    "nerfhip_mesh_view_rays": [_c_void_p, _i64, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _f32, _int, _int, _c_void_p, _f32,
+                               _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_color_accumulate": [_c_void_p, _c_void_p, _c_void_p, _i64, _f32, _c_void_p, _c_void_p],
+    "nerfhip_mesh_color_finish": [_c_void_p, _i64, _c_void_p, _c_void_p],
+    "nerfhip_mesh_rgb_to_u8": [_c_void_p, _i64, _c_void_p, _c_void_p],
 }
 
 
@@ -146,7 +161,8 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_mlp_act_bytes": ctypes.c_size_t, "nerfhip_mlp_packed_bwd_bytes": ctypes.c_size_t,
              "nerfhip_mlp_dy_bytes": ctypes.c_size_t, "nerfhip_mlp_dw_workspace_bytes": ctypes.c_size_t,
              "nerfhip_mlp_dw_workspace_bytes_multi": ctypes.c_size_t,
-             "nerfhip_linear_bwd_weight_workspace_bytes": ctypes.c_size_t}
+             "nerfhip_linear_bwd_weight_workspace_bytes": ctypes.c_size_t,
+             "nerfhip_marching_cubes_workspace_bytes": ctypes.c_size_t, "nerfhip_mesh_cluster_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 

@@ -938,3 +938,163 @@ def linear_act(xs, weight, bias, act, dtype):
     """nn.Linear (+ activation) on the concatenation of the (n, c_i) tensors `xs` (nerf.py:59-81, 108-118), differentiable in
     weight, bias and every segment.  act: ACT_NONE | ACT_RELU | ACT_SIGMOID."""
     return _LinearAct.apply(int(act), dtype, weight, bias, *xs)
+
+
+# ------------------------------------------------------------------------------- mesh extraction (extract_color_mesh.py:144-285)
+_INT32_MAX = 2 ** 31 - 1
+
+
+def _require_mesh(name, t, dtype, shape_len=None, cols=None):
+    if not torch.is_tensor(t):
+        raise NerfHipError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
+    if not t.is_cuda:
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: %s is a %s tensor (no CPU fallback)" % (name, t.device))
+    if t.dtype != dtype:
+        raise NerfHipError("%s: expected %s, got %s" % (name, dtype, t.dtype))
+    if shape_len is not None and t.dim() != shape_len:
+        raise NerfHipError("%s: expected rank %d, got shape %s" % (name, shape_len, tuple(t.shape)))
+    if cols is not None and t.shape[-1] != cols:
+        raise NerfHipError("%s: expected %d columns, got shape %s" % (name, cols, tuple(t.shape)))
+    return _c(t)
+
+
+def _check_vertex_ids(triangles, V):
+    if triangles.numel() and (int(triangles.min()) < 0 or int(triangles.max()) >= V):
+        raise NerfHipError("triangles reference vertices outside [0, %d)" % V)
+
+
+@device_guard
+def marching_cubes(volume, iso):
+    """nerfhip_marching_cubes_{count,emit}: (vertices (V,3) float64 in index coordinates, triangles (T,3) int32), on the device.
+    One 16-byte device-to-host read of (V, T) between the two launches sizes the outputs."""
+    volume = _require_mesh("marching_cubes volume", volume, torch.float32, 3)
+    n0, n1, n2 = volume.shape
+    if min(n0, n1, n2) < 2:
+        raise NerfHipError("marching_cubes: every dimension must be >= 2, got %s" % (tuple(volume.shape),))
+    lib = _lib.load()
+    ws_bytes = lib.nerfhip_marching_cubes_workspace_bytes(n0, n1, n2)
+    if ws_bytes == 0:
+        raise NerfHipError("marching_cubes: volume %s has 2^31 or more lattice points" % (tuple(volume.shape),))
+    ws = torch.empty(ws_bytes, device=volume.device, dtype=torch.uint8)
+    totals = torch.empty(2, device=volume.device, dtype=torch.int64)
+    check(lib.nerfhip_marching_cubes_count(ptr(volume), n0, n1, n2, float(iso), ptr(ws), ptr(totals), stream_ptr()),
+          "nerfhip_marching_cubes_count")
+    V, T = (int(x) for x in totals.cpu())
+    if V > _INT32_MAX or T > _INT32_MAX:
+        raise NerfHipError("marching_cubes: %d vertices / %d triangles do not fit int32" % (V, T))
+    verts = torch.empty(V, 3, device=volume.device, dtype=torch.float64)
+    tris = torch.empty(T, 3, device=volume.device, dtype=torch.int32)
+    if V or T:
+        check(lib.nerfhip_marching_cubes_emit(ptr(volume), n0, n1, n2, float(iso), ptr(ws), ptr(totals), ptr(verts), ptr(tris),
+                                              stream_ptr()), "nerfhip_marching_cubes_emit")
+    return verts, tris
+
+
+@device_guard
+def largest_cluster(triangles, n_vertices):
+    """(kept_vertex_ids (V',) int64 ascending, kept_triangles (T',3) int32 remapped) of the largest edge-connected cluster."""
+    triangles = _require_mesh("triangles", triangles, torch.int32, 2, 3)
+    T, V = triangles.shape[0], int(n_vertices)
+    dev = triangles.device
+    if T == 0 or V == 0:
+        return torch.empty(0, device=dev, dtype=torch.int64), torch.empty(0, 3, device=dev, dtype=torch.int32)
+    if V > _INT32_MAX or 3 * T > _INT32_MAX:
+        raise NerfHipError("largest_cluster: mesh too large (V=%d, T=%d)" % (V, T))
+    _check_vertex_ids(triangles, V)
+    lib = _lib.load()
+    keys = torch.empty(3 * T, device=dev, dtype=torch.int64)
+    check(lib.nerfhip_mesh_edge_keys(ptr(triangles), T, ptr(keys), stream_ptr()), "nerfhip_mesh_edge_keys")
+    sorted_keys, order = torch.sort(keys, stable=True)
+    ws = torch.empty(lib.nerfhip_mesh_cluster_workspace_bytes(V, T), device=dev, dtype=torch.uint8)
+    totals = torch.empty(3, device=dev, dtype=torch.int64)
+    check(lib.nerfhip_mesh_largest_cluster(ptr(triangles), V, T, ptr(sorted_keys), ptr(order), ptr(ws), ptr(totals), stream_ptr()),
+          "nerfhip_mesh_largest_cluster")
+    t_kept, v_kept, status = (int(x) for x in totals.cpu())
+    if status:
+        raise NerfHipError("largest_cluster: the union-find gave up after its retry bound")
+    kept_ids = torch.empty(v_kept, device=dev, dtype=torch.int64)
+    kept_tris = torch.empty(t_kept, 3, device=dev, dtype=torch.int32)
+    check(lib.nerfhip_mesh_cluster_compact(ptr(triangles), V, T, ptr(ws), ptr(kept_ids), ptr(kept_tris), stream_ptr()),
+          "nerfhip_mesh_cluster_compact")
+    return kept_ids, kept_tris
+
+
+@device_guard
+def vertex_normals(vertices, triangles):
+    """open3d's compute_vertex_normals on float32 vertices: (V,3) float64 unit normals ((0,0,1) where the sum is zero)."""
+    vertices = _require_mesh("vertices", vertices, torch.float32, 2, 3)
+    triangles = _require_mesh("triangles", triangles, torch.int32, 2, 3)
+    V, T = vertices.shape[0], triangles.shape[0]
+    out = torch.empty(V, 3, device=vertices.device, dtype=torch.float64)
+    if V == 0:
+        return out
+    _check_vertex_ids(triangles, V)
+    check(_lib.load().nerfhip_mesh_vertex_normals(ptr(vertices), V, ptr(triangles), T, ptr(out), stream_ptr()),
+          "nerfhip_mesh_vertex_normals")
+    return out
+
+
+@device_guard
+def normal_rays(vertices, normals, near, far, near_t):
+    vertices = _require_mesh("vertices", vertices, torch.float32, 2, 3)
+    normals = _require_mesh("normals", normals, torch.float64, 2, 3)
+    V = vertices.shape[0]
+    rays = torch.empty(V, 8, device=vertices.device, dtype=torch.float32)
+    if V:
+        check(_lib.load().nerfhip_mesh_normal_rays(ptr(vertices), ptr(normals), V, float(near), float(far), float(near_t), ptr(rays),
+                                                   stream_ptr()), "nerfhip_mesh_normal_rays")
+    return rays
+
+
+@device_guard
+def view_rays(vertices, w2c, origin, focal, image, near):
+    """One view: (colors (V,4) uint8, depth (V,) float64, rays (V,8) float32).  w2c: (3,4) float32 numpy, origin: (3,) float32."""
+    import numpy as np
+    vertices = _require_mesh("vertices", vertices, torch.float32, 2, 3)
+    image = _require_mesh("image", image, torch.uint8, 3, 3)
+    H, W = image.shape[0], image.shape[1]
+    V = vertices.shape[0]
+    dev = vertices.device
+    colors = torch.empty(V, 4, device=dev, dtype=torch.uint8)
+    depth = torch.empty(V, device=dev, dtype=torch.float64)
+    rays = torch.empty(V, 8, device=dev, dtype=torch.float32)
+    if V:
+        w = np.ascontiguousarray(np.asarray(w2c, np.float32).reshape(3, 4))
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+        fp = ctypes.POINTER(ctypes.c_float)
+        check(_lib.load().nerfhip_mesh_view_rays(ptr(vertices), V, w.ctypes.data_as(fp), o.ctypes.data_as(fp), float(np.float32(focal)),
+                                                 W, H, ptr(image), float(near), ptr(colors), ptr(depth), ptr(rays), stream_ptr()),
+              "nerfhip_mesh_view_rays")
+    return colors, depth, rays
+
+
+@device_guard
+def color_accumulate(colors, depth, opacity, occ_threshold, accum):
+    colors = _require_mesh("colors", colors, torch.uint8, 2, 4)
+    depth = _require_mesh("depth", depth, torch.float64, 1)
+    opacity = _require_mesh("opacity", opacity, torch.float32, 1)
+    accum = _require_mesh("accum", accum, torch.float64, 2, 4)
+    V = colors.shape[0]
+    if V:
+        check(_lib.load().nerfhip_mesh_color_accumulate(ptr(colors), ptr(depth), ptr(opacity), V, float(occ_threshold), ptr(accum),
+                                                        stream_ptr()), "nerfhip_mesh_color_accumulate")
+    return accum
+
+
+@device_guard
+def color_finish(accum):
+    accum = _require_mesh("accum", accum, torch.float64, 2, 4)
+    V = accum.shape[0]
+    out = torch.empty(V, 3, device=accum.device, dtype=torch.uint8)
+    if V:
+        check(_lib.load().nerfhip_mesh_color_finish(ptr(accum), V, ptr(out), stream_ptr()), "nerfhip_mesh_color_finish")
+    return out
+
+
+@device_guard
+def rgb_to_u8(rgb):
+    rgb = _require_mesh("rgb", rgb, torch.float32)
+    out = torch.empty(rgb.shape, device=rgb.device, dtype=torch.uint8)
+    if rgb.numel():
+        check(_lib.load().nerfhip_mesh_rgb_to_u8(ptr(rgb), rgb.numel(), ptr(out), stream_ptr()), "nerfhip_mesh_rgb_to_u8")
+    return out
