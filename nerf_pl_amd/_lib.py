@@ -5,6 +5,7 @@ on a non-GPU tensor, this raises.  torch is imported first so that the library's
 libamdhip64.so.7 dependency binds to the HIP runtime torch already loaded (one runtime per process).
 """
 import ctypes
+import functools
 import os
 
 import torch  # noqa: F401  (must precede the dlopen below)
@@ -218,8 +219,6 @@ def device_guard(fn):
     """Run `fn` with the device of its first CUDA tensor argument as the current device (what ATen's ops do
     implicitly): the HIP launch and `stream_ptr()` then refer to the GPU that owns the buffers, also when the
     caller's current device is a different one."""
-    import functools
-
     @functools.wraps(fn)
     def wrapped(*args, **kw):
         t = _first_cuda_tensor(args)

@@ -10,6 +10,7 @@ from . import ops
 class MSELoss(nn.Module):
     def __init__(self):
         super(MSELoss, self).__init__()
+        # not used by forward(): it is the attribute the reference's MSELoss has (losses.py:7), so part of the drop-in surface — keep
         self.loss = nn.MSELoss(reduction='mean')
         self.last = None          # [loss, psnr(fine|coarse), mse] of the last forward (detached device tensor)
 

@@ -112,6 +112,22 @@ class NeRF(nn.Module):
             self._packed_cache["args"] = hit
         return hit[1], hit[2], ps[0].device
 
+    def _require_default_arch(self):
+        if not self.is_default_arch():
+            raise NotImplementedError(ops.DEFAULT_ARCH_ONLY)
+
+    def _fwd_buffer(self, dtype, dev):
+        buf = self._packed_cache.get(dtype)
+        if buf is None or buf.device != dev:
+            buf = self._packed_cache[dtype] = torch.empty(ops.packed_bytes(dtype), device=dev, dtype=torch.uint8)
+        return buf
+
+    def _bwd_buffer(self, dtype, dev):
+        buf = self._packed_cache.get(("bwd", dtype))
+        if buf is None or buf.device != dev:
+            buf = self._packed_cache[("bwd", dtype)] = torch.empty(ops.packed_bwd_bytes(dtype), device=dev, dtype=torch.uint8)
+        return buf
+
     def packed_weights(self, dtype=None):
         """MFMA-fragment-ordered image of the CURRENT parameters (one ~5 us HIP launch into a reused buffer).
 
@@ -119,21 +135,11 @@ class NeRF(nn.Module):
         (`torch.optim.Adam(fused=True)`) update parameters without bumping `_version`, and a stale image would
         silently render/train with old weights.  Callers that know the weights are frozen (an eval loop) can hold
         on to the returned buffer."""
-        if not self.is_default_arch():
-            raise NotImplementedError("the fused HIP MLP implements the reference's default architecture "
-                                      "(D=8, W=256, skips=[4], 63/27 inputs) only")
+        self._require_default_arch()
         dtype = dtype or self.mlp_dtype
         wp, bp, dev = self._pack_args()
-        buf = self._packed_cache.get(dtype)
-        if buf is None or buf.device != dev:
-            buf = self._packed_cache[dtype] = torch.empty(ops.packed_bytes(dtype), device=dev, dtype=torch.uint8)
+        buf = self._fwd_buffer(dtype, dev)
         ops.pack_weights_raw(wp, bp, buf, dtype)
-        return buf
-
-    def _bwd_buffer(self, dtype, dev):
-        buf = self._packed_cache.get(("bwd", dtype))
-        if buf is None or buf.device != dev:
-            buf = self._packed_cache[("bwd", dtype)] = torch.empty(ops.packed_bwd_bytes(dtype), device=dev, dtype=torch.uint8)
         return buf
 
     def packed_weights_bwd(self, dtype=None):
@@ -146,10 +152,7 @@ class NeRF(nn.Module):
 
     def train_buffers(self, dtype, dev):
         """(forward image buffer, W^T image buffer) of this model, allocated once per (dtype, device)."""
-        buf = self._packed_cache.get(dtype)
-        if buf is None or buf.device != dev:
-            buf = self._packed_cache[dtype] = torch.empty(ops.packed_bytes(dtype), device=dev, dtype=torch.uint8)
-        return buf, self._bwd_buffer(dtype, dev)
+        return self._fwd_buffer(dtype, dev), self._bwd_buffer(dtype, dev)
 
     def packed_weights_train(self, dtype=None):
         """(forward image, W^T image) of the current parameters in ONE launch: a training forward packs both, its backward
@@ -157,15 +160,10 @@ class NeRF(nn.Module):
         That is harmless while the weights are unchanged (identical images) and WRONG if an optimizer stepped in between —
         PyTorch raises for its own saved tensors in that situation; here it is detected only for optimizers that announce their
         updates (FlatAdam bumps `_weights_serial`; `check_pack_serial` in the backward), not for foreign in-place updates."""
-        if not self.is_default_arch():
-            raise NotImplementedError("the fused HIP MLP implements the reference's default architecture "
-                                      "(D=8, W=256, skips=[4], 63/27 inputs) only")
+        self._require_default_arch()
         dtype = dtype or self.mlp_dtype
         wp, bp, dev = self._pack_args()
-        buf = self._packed_cache.get(dtype)
-        if buf is None or buf.device != dev:
-            buf = self._packed_cache[dtype] = torch.empty(ops.packed_bytes(dtype), device=dev, dtype=torch.uint8)
-        bwd = self._bwd_buffer(dtype, dev)
+        buf, bwd = self.train_buffers(dtype, dev)
         ops.pack_weights_train_raw(wp, bp, buf, bwd, dtype)
         self._packed_serial = getattr(self, "_weights_serial", 0)
         return buf, bwd

@@ -69,6 +69,14 @@ def _mlp_points(model, embedding_xyz, rays, z, dir_embedded, sigma_only, chunk):
     return out.view(B, S) if sigma_only else out.view(B, S, 4)
 
 
+def _result(test_time, rgb_c, depth_c, opacity_c, fine=None):
+    """render_rays' dict (rendering.py:213-244): the coarse pass leaves only its opacity at test time; fine = (rgb, depth, opacity)"""
+    result = {'opacity_coarse': opacity_c} if test_time else {'rgb_coarse': rgb_c, 'depth_coarse': depth_c, 'opacity_coarse': opacity_c}
+    if fine is not None:
+        result.update(rgb_fine=fine[0], depth_fine=fine[1], opacity_fine=fine[2])
+    return result
+
+
 def render_rays(models,
                 embeddings,
                 rays,
@@ -104,35 +112,9 @@ def render_rays(models,
         def mlp(model, z, sigma_only):
             return _mlp_points(model, embeddings[0], rays, z, dir_embedded, sigma_only, int(chunk))
 
-    # ---- the whole call in ONE launch (nerfhip_render_fwd) where nothing needs a gradient and the shape fits the kernel's ray
-    # groups: the same four draws in the same order first, then workgroups that own 4 rays each run coarse MLP -> compositing ->
-    # fine depths -> fine MLP -> compositing (csrc/mlp_render_kernel.h; bit-identical to the launches below)
-    if (dev.type == "cuda" and _fusable(models, embeddings) and not (torch.is_grad_enabled() and any(_needs_grad(m) for m in models[:2]))
-            and (N_importance == 0 or models[0].mlp_dtype == models[1].mlp_dtype)
-            and (not test_time or (FUSE_TEST_TIME and N_importance > 0))
-            and ops.render_supported(N_rays, N_samples, N_importance, model_coarse.mlp_dtype)):
-        graph_rng = D.in_graph_stream(dev)
-        rnd = (lambda *sh: D.rand(sh, dev)) if graph_rng else (lambda *sh: torch.rand(*sh, device=dev))
-        rndn = (lambda *sh: D.randn(sh, dev)) if graph_rng else (lambda *sh: torch.randn(*sh, device=dev))
-        perturb_rand = rnd(N_rays, N_samples) if perturb > 0 else None                     # :203
-        noise_c = rndn(N_rays, N_samples)                                                  # :152 (always drawn)
-        u = noise_f = None
-        if N_importance > 0:
-            u = rnd(N_rays, N_importance) if perturb != 0 else None                        # :39
-            noise_f = rndn(N_rays, N_samples + N_importance)                               # :152
-        dtype = model_coarse.mlp_dtype
-        out = ops.render_fwd(rays, N_samples, N_importance, model_coarse.packed_weights(dtype),
-                             models[1].packed_weights(dtype) if N_importance > 0 else None, dtype, use_disp, perturb, perturb_rand,
-                             noise_c, noise_f, noise_std, white_back, u, want_coarse=not test_time, test_time=test_time)
-        result = {'opacity_coarse': out['opacity_coarse']} if test_time else \
-            {'rgb_coarse': out['rgb_coarse'], 'depth_coarse': out['depth_coarse'], 'opacity_coarse': out['opacity_coarse']}
-        if N_importance > 0:
-            result.update(rgb_fine=out['rgb_fine'], depth_fine=out['depth_fine'], opacity_fine=out['opacity_fine'])
-        return result
-
-    # RNG: identical calls, order, shapes and device as the reference.  Inside a hipGraph capture that owns a
-    # device-resident generator state (system.GraphedTrainStep: its batch source draws through draws.py) these four come from the
-    # same state — torch's own capture-time bookkeeping would restart every replay at the offset that state starts from.
+    # RNG: identical calls, order, shapes and device as the reference, in both forms below.  Inside a hipGraph capture
+    # that owns a device-resident generator state (system.GraphedTrainStep: its batch source draws through draws.py) these four come
+    # from the same state — torch's own capture-time bookkeeping would restart every replay at the offset that state starts from.
     graph_rng = dev.type == "cuda" and D.in_graph_stream(dev)
 
     def rand(*shape):
@@ -140,17 +122,37 @@ def render_rays(models,
 
     def randn(*shape):
         return D.randn(shape, dev) if graph_rng else torch.randn(*shape, device=dev)
+
+    # ---- the whole call in ONE launch (nerfhip_render_fwd) where nothing needs a gradient and the shape fits the kernel's ray
+    # groups: the same four draws in the same order first, then workgroups that own 4 rays each run coarse MLP -> compositing ->
+    # fine depths -> fine MLP -> compositing (csrc/mlp_render_kernel.h; bit-identical to the launches below)
+    if (dev.type == "cuda" and _fusable(models, embeddings) and not (torch.is_grad_enabled() and any(_needs_grad(m) for m in models[:2]))
+            and (N_importance == 0 or models[0].mlp_dtype == models[1].mlp_dtype)
+            and (not test_time or (FUSE_TEST_TIME and N_importance > 0))
+            and ops.render_supported(N_rays, N_samples, N_importance, model_coarse.mlp_dtype)):
+        perturb_rand = rand(N_rays, N_samples) if perturb > 0 else None                    # :203
+        noise_c = randn(N_rays, N_samples)                                                 # :152 (always drawn)
+        u = noise_f = None
+        if N_importance > 0:
+            u = rand(N_rays, N_importance) if perturb != 0 else None                       # :39
+            noise_f = randn(N_rays, N_samples + N_importance)                              # :152
+        dtype = model_coarse.mlp_dtype
+        out = ops.render_fwd(rays, N_samples, N_importance, model_coarse.packed_weights(dtype),
+                             models[1].packed_weights(dtype) if N_importance > 0 else None, dtype, use_disp, perturb, perturb_rand,
+                             noise_c, noise_f, noise_std, white_back, u, want_coarse=not test_time, test_time=test_time)
+        return _result(test_time, out.get('rgb_coarse'), out.get('depth_coarse'), out['opacity_coarse'],
+                       (out['rgb_fine'], out['depth_fine'], out['opacity_fine']) if N_importance > 0 else None)
+
     perturb_rand = rand(N_rays, N_samples) if perturb > 0 else None                        # :203
     z_vals = ops.sample_coarse_z(rays, N_samples, use_disp, perturb, perturb_rand)          # :189-204
     noise_c = randn(N_rays, N_samples)                                                      # :152 (always drawn)
 
     raw_c = mlp(model_coarse, z_vals, bool(test_time))                                      # :206-217
+    rgb_c = depth_c = fine = None
     if test_time:
         weights_coarse, opacity_c = ops.composite(raw_c, z_vals, rays, noise_c, noise_std, white_back)
-        result = {'opacity_coarse': opacity_c}
     else:
         weights_coarse, opacity_c, rgb_c, depth_c = ops.composite(raw_c, z_vals, rays, noise_c, noise_std, white_back)
-        result = {'rgb_coarse': rgb_c, 'depth_coarse': depth_c, 'opacity_coarse': opacity_c}
 
     if N_importance > 0:                                                                    # :222-242
         u = rand(N_rays, N_importance) if perturb != 0 else None                            # :39, det=(perturb==0)
@@ -158,8 +160,5 @@ def render_rays(models,
         noise_f = randn(N_rays, N_samples + N_importance)                                   # :152
         raw_f = mlp(models[1], z_fine, False)
         _, opacity_f, rgb_f, depth_f = ops.composite(raw_f, z_fine, rays, noise_f, noise_std, white_back)
-        result['rgb_fine'] = rgb_f
-        result['depth_fine'] = depth_f
-        result['opacity_fine'] = opacity_f
-
-    return result
+        fine = (rgb_f, depth_f, opacity_f)
+    return _result(test_time, rgb_c, depth_c, opacity_c, fine)

@@ -28,6 +28,92 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+# ------------------------------------------------------------------------------- argument rules shared by the operators
+# Each helper returns the (contiguous) TENSOR, never only its pointer: the caller keeps it alive across the C call.
+def _check_draw(op, name, t, numel):
+    """caller-supplied draw tensors (batch['draws'] may have been made for other hyper-parameters): a wrong size would be an
+    out-of-bounds device read, not an error"""
+    if t is not None and (t.numel() != numel or t.dtype != torch.float32):
+        raise ValueError("%s: %s must hold %d fp32 draws, got %s %s" % (op, name, numel, tuple(t.shape), t.dtype))
+
+
+def _noise_arg(op, name, noise, noise_std, numel):
+    """rendering.py:152-153: noise_std == 0 means no noise, whatever was drawn; else `numel` fp32 draws (or None)"""
+    if noise_std == 0 or noise is None:
+        return None
+    noise = _c(noise)
+    _check_draw(op, name, noise, numel)
+    return noise
+
+
+def _u_arg(op, u, B, K):
+    """sample_pdf's uniforms: None (deterministic linspace), (K,) shared by every ray, or (B,K).  Returns (u, row stride)."""
+    if u is None:
+        return None, 0
+    if tuple(u.shape) not in ((B, K), (K,)) or u.dtype != torch.float32:
+        raise ValueError("%s: u must be (N_importance,) or (B, N_importance) = (%d, %d) fp32, got %s %s"
+                         % (op, B, K, tuple(u.shape), u.dtype))
+    return _c(u), (K if u.dim() == 2 else 0)
+
+
+def _perturb_arg(op, perturb, perturb_rand, numel):
+    """rendering.py:199-204: the B*S uniforms are read only when perturb > 0, and are needed then"""
+    if not perturb > 0:
+        return None
+    if perturb_rand is None:
+        raise ValueError("%s: perturb>0 needs perturb_rand" % op)
+    perturb_rand = _c(perturb_rand)
+    _check_draw(op, "perturb_rand", perturb_rand, numel)
+    return perturb_rand
+
+
+def _train_composite_args(op, raw, z, rays, target):
+    """contiguous (raw (B,S,4), z (B,S), rays, target (B,3)) of the composite_train* operators + B, S"""
+    raw, z, rays, target = _c(raw), _c(z), _c(rays), _c(target)
+    B, S = z.shape
+    if raw.numel() != B * S * 4 or target.numel() != B * 3:
+        raise ValueError("%s: raw must be (B,S,4) and target (B,3)" % op)
+    return raw, z, rays, target, B, S
+
+
+def _train_composite_outs(B, S, dev):
+    """(opacity (B,), rgb (B,3), depth (B,), g_raw (B,S,4)) that every composite_train* launch writes"""
+    f32 = dict(device=dev, dtype=torch.float32)
+    return torch.empty(B, **f32), torch.empty(B, 3, **f32), torch.empty(B, **f32), torch.empty(B, S, 4, **f32)
+
+
+# ticket words of the arrival-ticket kernels (composite_train_loss, render_train_fwd)
+_TICKETS = {}
+_CAPTURES = {}
+_EAGER_SLOTS = {}
+_TICKET_WORDS = 1024
+
+
+def _ticket(device):
+    """One zero-initialised device word for the arrival-ticket kernels (they leave it at zero).  Eager launches on one stream are
+    ordered and share the word of their (GPU, stream).  A hipGraph is different: it is replayed on whatever stream is current then,
+    so two graphs CAPTURED on one stream may run concurrently — every capture therefore gets a word of its own (ADVICE r5): a new
+    capture is recognised by the stream's capture status going from "none" to "active" between two calls.
+    Known defect, left as it is here: captures on different streams can share a slot (first finding)."""
+    st = torch.cuda.current_stream(device)
+    capturing = torch.cuda.is_current_stream_capturing()
+    rec = _CAPTURES.setdefault((device.index, st.stream_id), [False, 0])
+    if capturing and not rec[0]:
+        rec[1] += 1
+    rec[0] = capturing
+    pool = _TICKETS.get(device.index)
+    if pool is None:
+        if capturing:
+            raise NerfHipError("the ticket words of this GPU must exist before a capture: run the step once eagerly first")
+        pool = _TICKETS[device.index] = torch.zeros(_TICKET_WORDS * 4, device=device, dtype=torch.int32)
+    # slots 0..31: eager use, one per stream in order of first use; 32..: captures, in order (16-byte pitch)
+    if capturing:
+        slot = 32 + rec[1] % (_TICKET_WORDS - 32)
+    else:
+        slot = _EAGER_SLOTS.setdefault((device.index, st.stream_id), len([k for k in _EAGER_SLOTS if k[0] == device.index]) % 32)
+    return pool[4 * slot:4 * slot + 4]
+
+
 # ------------------------------------------------------------------------------- posenc (a2)
 class _PosEnc(torch.autograd.Function):
     @staticmethod
@@ -72,14 +158,10 @@ def sample_coarse_z(rays, n_samples, use_disp=False, perturb=0.0, perturb_rand=N
     require_gpu(rays, perturb_rand)
     rays = _c(rays)
     B = rays.shape[0]
+    perturb_rand = _perturb_arg("sample_coarse_z", perturb, perturb_rand, B * n_samples)
     z = torch.empty(B, n_samples, device=rays.device, dtype=torch.float32)
-    if perturb > 0:
-        if perturb_rand is None:
-            raise ValueError("perturb>0 needs perturb_rand")
-        perturb_rand = _c(perturb_rand)
-    check(_lib.load().nerfhip_sample_coarse_z(ptr(rays), ptr(perturb_rand if perturb > 0 else None), ptr(z), B,
-                                              n_samples, int(bool(use_disp)), float(perturb), stream_ptr()),
-          "nerfhip_sample_coarse_z")
+    check(_lib.load().nerfhip_sample_coarse_z(ptr(rays), ptr(perturb_rand), ptr(z), B, n_samples, int(bool(use_disp)),
+                                              float(perturb), stream_ptr()), "nerfhip_sample_coarse_z")
     return z
 
 
@@ -138,15 +220,7 @@ def sample_pdf_u(bins, weights, n_importance, u=None, eps=1e-5, return_cdf_inds=
     B, M = weights.shape
     if bins.shape != (B, M + 1):
         raise ValueError("bins must be (N_rays, N_samples_+1)")
-    u_stride = 0
-    if u is not None:
-        u = _c(u)
-        if u.dim() == 2:
-            if u.shape != (B, n_importance):
-                raise ValueError("u must be (B, N_importance)")
-            u_stride = n_importance
-        elif u.shape != (n_importance,):
-            raise ValueError("u must be (N_importance,) or (B, N_importance)")
+    u, u_stride = _u_arg("sample_pdf", u, B, n_importance)
     samples = torch.empty(B, n_importance, device=bins.device, dtype=torch.float32)
     cdf = torch.empty(B, M + 1, device=bins.device, dtype=torch.float32) if return_cdf_inds else None
     inds = torch.empty(B, n_importance, device=bins.device, dtype=torch.int64) if return_cdf_inds else None
@@ -164,10 +238,7 @@ def fine_z(z_coarse, w_coarse, n_importance, u=None, eps=1e-5, return_new=False,
     require_gpu(z_coarse, w_coarse, u)
     z_coarse, w_coarse = _c(z_coarse), _c(w_coarse)
     B, S = z_coarse.shape
-    u_stride = 0
-    if u is not None:
-        u = _c(u)
-        u_stride = n_importance if u.dim() == 2 else 0
+    u, u_stride = _u_arg("fine_z", u, B, n_importance)
     zf = torch.empty(B, S + n_importance, device=z_coarse.device, dtype=torch.float32)
     zn = torch.empty(B, n_importance, device=z_coarse.device, dtype=torch.float32) if return_new else None
     cdf = torch.empty(B, S - 1, device=z_coarse.device, dtype=torch.float32) if return_cdf_inds else None
@@ -239,20 +310,10 @@ def composite_train(raw, z, rays, noise, noise_std, white_back, target, grad_sca
     (nerfhip_composite_train).  Returns (weights | None, opacity, rgb, depth, g_raw = d loss / d raw); nothing is recorded for
     autograd — the caller (models/train_step.py) owns the backward."""
     require_gpu(raw, z, rays, noise, target)
-    raw, z, rays, target = _c(raw), _c(z), _c(rays), _c(target)
-    B, S = z.shape
-    if raw.numel() != B * S * 4 or target.numel() != B * 3:
-        raise ValueError("composite_train: raw must be (B,S,4) and target (B,3)")
-    if noise_std == 0:
-        noise = None
-    elif noise is not None:
-        noise = _c(noise)
-    dev = z.device
-    weights = torch.empty(B, S, device=dev, dtype=torch.float32) if want_weights else None
-    opacity = torch.empty(B, device=dev, dtype=torch.float32)
-    rgb = torch.empty(B, 3, device=dev, dtype=torch.float32)
-    depth = torch.empty(B, device=dev, dtype=torch.float32)
-    g_raw = torch.empty(B, S, 4, device=dev, dtype=torch.float32)
+    raw, z, rays, target, B, S = _train_composite_args("composite_train", raw, z, rays, target)
+    noise = _noise_arg("composite_train", "noise", noise, noise_std, B * S)
+    weights = torch.empty(B, S, device=z.device, dtype=torch.float32) if want_weights else None
+    opacity, rgb, depth, g_raw = _train_composite_outs(B, S, z.device)
     check(_lib.load().nerfhip_composite_train(ptr(raw), ptr(z), ptr(rays), ptr(noise), float(noise_std), int(bool(white_back)),
                                               ptr(target), float(grad_scale), ptr(weights), ptr(rgb), ptr(depth), ptr(opacity),
                                               ptr(g_raw), B, S, stream_ptr()), "nerfhip_composite_train")
@@ -265,23 +326,12 @@ def composite_train_fine_z(raw, z, rays, noise, noise_std, white_back, target, g
     """The coarse pass of a training step in one launch (nerfhip_composite_train_fine_z): composite_train + fine_z on the
     ray's weights (which stay in LDS unless want_weights).  Returns (weights | None, opacity, rgb, depth, g_raw, z_fine)."""
     require_gpu(raw, z, rays, noise, target, u)
-    raw, z, rays, target = _c(raw), _c(z), _c(rays), _c(target)
-    B, S = z.shape
-    if raw.numel() != B * S * 4 or target.numel() != B * 3:
-        raise ValueError("composite_train_fine_z: raw must be (B,S,4) and target (B,3)")
-    noise = None if noise_std == 0 else (_c(noise) if noise is not None else None)
-    _check_draw("composite_train_fine_z", "noise", noise, B * S)
-    u_stride = 0
-    if u is not None:
-        u = _c(u)
-        u_stride = n_importance if u.dim() == 2 else 0
-        _check_draw("composite_train_fine_z", "u", u, B * n_importance if u.dim() == 2 else n_importance)
+    raw, z, rays, target, B, S = _train_composite_args("composite_train_fine_z", raw, z, rays, target)
+    noise = _noise_arg("composite_train_fine_z", "noise", noise, noise_std, B * S)
+    u, u_stride = _u_arg("composite_train_fine_z", u, B, n_importance)
     dev = z.device
     weights = torch.empty(B, S, device=dev, dtype=torch.float32) if want_weights else None
-    opacity = torch.empty(B, device=dev, dtype=torch.float32)
-    rgb = torch.empty(B, 3, device=dev, dtype=torch.float32)
-    depth = torch.empty(B, device=dev, dtype=torch.float32)
-    g_raw = torch.empty(B, S, 4, device=dev, dtype=torch.float32)
+    opacity, rgb, depth, g_raw = _train_composite_outs(B, S, dev)
     zf = torch.empty(B, S + n_importance, device=dev, dtype=torch.float32)
     check(_lib.load().nerfhip_composite_train_fine_z(ptr(raw), ptr(z), ptr(rays), ptr(noise), float(noise_std), int(bool(white_back)),
                                                      ptr(target), float(grad_scale), ptr(weights), ptr(rgb), ptr(depth), ptr(opacity),
@@ -290,64 +340,24 @@ def composite_train_fine_z(raw, z, rays, noise, noise_std, white_back, target, g
     return weights, opacity, rgb, depth, g_raw, zf
 
 
-_TICKETS = {}
-_CAPTURES = {}
-_EAGER_SLOTS = {}
-_TICKET_WORDS = 1024
-
-
-def _check_draw(op, name, t, numel):
-    """caller-supplied draw tensors (batch['draws'] may have been made for other hyper-parameters): a wrong size would be an
-    out-of-bounds device read, not an error"""
-    if t is not None and (t.numel() != numel or t.dtype != torch.float32):
-        raise ValueError("%s: %s must hold %d fp32 draws, got %s %s" % (op, name, numel, tuple(t.shape), t.dtype))
-
-
-def _ticket(device):
-    """One zero-initialised device word for the arrival-ticket kernels (they leave it at zero).  Eager launches on one stream are
-    ordered and share the word of their (GPU, stream).  A hipGraph is different: it is replayed on whatever stream is current then,
-    so two graphs CAPTURED on one stream may run concurrently — every capture therefore gets a word of its own (ADVICE r5): a new
-    capture is recognised by the stream's capture status going from "none" to "active" between two calls."""
-    st = torch.cuda.current_stream(device)
-    capturing = torch.cuda.is_current_stream_capturing()
-    rec = _CAPTURES.setdefault((device.index, st.stream_id), [False, 0])
-    if capturing and not rec[0]:
-        rec[1] += 1
-    rec[0] = capturing
-    pool = _TICKETS.get(device.index)
-    if pool is None:
-        if capturing:
-            raise NerfHipError("the ticket words of this GPU must exist before a capture: run the step once eagerly first")
-        pool = _TICKETS[device.index] = torch.zeros(_TICKET_WORDS * 4, device=device, dtype=torch.int32)
-    # slots 0..31: eager use, one per stream in order of first use; 32..: captures, in order (16-byte pitch)
-    if capturing:
-        slot = 32 + rec[1] % (_TICKET_WORDS - 32)
-    else:
-        slot = _EAGER_SLOTS.setdefault((device.index, st.stream_id), len([k for k in _EAGER_SLOTS if k[0] == device.index]) % 32)
-    return pool[4 * slot:4 * slot + 4]
-
-
 @device_guard
 def composite_train_loss(raw, z, rays, noise, noise_std, white_back, target, grad_scale, rgb_coarse=None):
     """The last pass of a training step in one launch (nerfhip_composite_train_loss): composite_train + the values of mse_psnr
     over (rgb_coarse, this pass's rgb).  Returns (opacity, rgb, depth, g_raw, out3 = [loss, psnr, mse])."""
     require_gpu(raw, z, rays, noise, target, rgb_coarse)
-    raw, z, rays, target = _c(raw), _c(z), _c(rays), _c(target)
-    B, S = z.shape
-    if raw.numel() != B * S * 4 or target.numel() != B * 3 or (rgb_coarse is not None and rgb_coarse.numel() != B * 3):
-        raise ValueError("composite_train_loss: raw must be (B,S,4), target and rgb_coarse (B,3)")
-    noise = None if noise_std == 0 else (_c(noise) if noise is not None else None)
-    _check_draw("composite_train_loss", "noise", noise, B * S)
+    raw, z, rays, target, B, S = _train_composite_args("composite_train_loss", raw, z, rays, target)
+    if rgb_coarse is not None:
+        rgb_coarse = _c(rgb_coarse)
+        if rgb_coarse.numel() != B * 3:
+            raise ValueError("composite_train_loss: rgb_coarse must be (B,3)")
+    noise = _noise_arg("composite_train_loss", "noise", noise, noise_std, B * S)
     dev = z.device
-    opacity = torch.empty(B, device=dev, dtype=torch.float32)
-    rgb = torch.empty(B, 3, device=dev, dtype=torch.float32)
-    depth = torch.empty(B, device=dev, dtype=torch.float32)
-    g_raw = torch.empty(B, S, 4, device=dev, dtype=torch.float32)
+    opacity, rgb, depth, g_raw = _train_composite_outs(B, S, dev)
     out3 = torch.empty(3, device=dev, dtype=torch.float32)
     check(_lib.load().nerfhip_composite_train_loss(ptr(raw), ptr(z), ptr(rays), ptr(noise), float(noise_std), int(bool(white_back)),
                                                    ptr(target), float(grad_scale), None, ptr(rgb), ptr(depth), ptr(opacity), ptr(g_raw),
-                                                   B, S, ptr(_c(rgb_coarse)) if rgb_coarse is not None else None, ptr(out3),
-                                                   ptr(_ticket(dev)), stream_ptr()), "nerfhip_composite_train_loss")
+                                                   B, S, ptr(rgb_coarse), ptr(out3), ptr(_ticket(dev)), stream_ptr()),
+          "nerfhip_composite_train_loss")
     return opacity, rgb, depth, g_raw, out3
 
 
@@ -429,34 +439,11 @@ PARAM_SHAPES = [(256, 63), (256, 256), (256, 256), (256, 256), (256, 319), (256,
                 (256, 256), (128, 283), (1, 256), (3, 128)]
 
 
+DEFAULT_ARCH_ONLY = "the fused HIP MLP implements the reference's default architecture (D=8, W=256, skips=[4], 63/27 inputs) only"
+
+
 def packed_bytes(dtype):
     return int(_lib.load().nerfhip_mlp_packed_bytes(mlp_dtype_code(dtype)))
-
-
-@device_guard
-def pack_weights(weights, biases, dtype, out=None):
-    """Repack 12 (weight, bias) fp32 tensors (state_dict order, PARAM_ORDER) into the MFMA A-fragment
-    stream of `dtype`.  Returns a uint8 device buffer."""
-    code = mlp_dtype_code(dtype)
-    if len(weights) != 12 or len(biases) != 12:
-        raise ValueError("need 12 weights and 12 biases")
-    keep = []
-    for i, (w, b) in enumerate(zip(weights, biases)):
-        require_gpu(w, b)
-        if tuple(w.shape) != PARAM_SHAPES[i] or tuple(b.shape) != (PARAM_SHAPES[i][0],):
-            raise NerfHipError("fused MLP supports the reference default architecture only "
-                               "(D=8, W=256, skips=[4], in 63/27); got %s for %s" % (tuple(w.shape), PARAM_ORDER[i]))
-        keep.append((_c(w.detach()), _c(b.detach())))
-    dev = keep[0][0].device
-    if out is None:
-        out = torch.empty(packed_bytes(dtype), device=dev, dtype=torch.uint8)
-    wp = (ctypes.c_void_p * 12)(*[k[0].data_ptr() for k in keep])
-    bp = (ctypes.c_void_p * 12)(*[k[1].data_ptr() for k in keep])
-    check(_lib.load().nerfhip_mlp_pack_weights(wp, bp, ptr(out), code, stream_ptr()), "nerfhip_mlp_pack_weights")
-    return out
-
-
-_SIZE_CACHE = {}
 
 
 def packed_bwd_bytes(dtype):
@@ -470,8 +457,7 @@ def pack_arg_tables(weights, biases):
     for i, (w, b) in enumerate(zip(weights, biases)):
         require_gpu(w, b)
         if tuple(w.shape) != PARAM_SHAPES[i] or tuple(b.shape) != (PARAM_SHAPES[i][0],):
-            raise NerfHipError("fused MLP supports the reference default architecture only "
-                               "(D=8, W=256, skips=[4], in 63/27); got %s for %s" % (tuple(w.shape), PARAM_ORDER[i]))
+            raise NerfHipError("%s; got %s for %s" % (DEFAULT_ARCH_ONLY, tuple(w.shape), PARAM_ORDER[i]))
         if not (w.is_contiguous() and b.is_contiguous()):
             raise NerfHipError("NeRF parameters must be contiguous")
     wp = (ctypes.c_void_p * 12)(*[w.data_ptr() for w in weights])
@@ -535,16 +521,10 @@ def mlp_fwd_rays_coarse(rays, n_samples, packed, sigma_only, dtype, use_disp=Fal
     require_gpu(rays, perturb_rand)
     rays = _c(rays)
     B, S = rays.shape[0], int(n_samples)
-    if perturb > 0:
-        if perturb_rand is None:
-            raise ValueError("perturb>0 needs perturb_rand")
-        perturb_rand = _c(perturb_rand)
-        if perturb_rand.numel() != B * S or perturb_rand.dtype != torch.float32:
-            raise ValueError("mlp_fwd_rays_coarse: perturb_rand must hold B*S = %d fp32 draws, got %s %s"
-                             % (B * S, tuple(perturb_rand.shape), perturb_rand.dtype))
+    perturb_rand = _perturb_arg("mlp_fwd_rays_coarse", perturb, perturb_rand, B * S)
     z = torch.empty(B, S, device=rays.device, dtype=torch.float32)
     out = torch.empty((B, S) if sigma_only else (B, S, 4), device=rays.device, dtype=torch.float32)
-    check(_lib.load().nerfhip_mlp_fwd_rays_coarse(ptr(rays), ptr(perturb_rand if perturb > 0 else None), ptr(z), B, S,
+    check(_lib.load().nerfhip_mlp_fwd_rays_coarse(ptr(rays), ptr(perturb_rand), ptr(z), B, S,
                                                   int(bool(use_disp)), float(perturb), ptr(packed), ptr(out), int(bool(sigma_only)),
                                                   mlp_dtype_code(dtype), ptr(save), stream_ptr()), "nerfhip_mlp_fwd_rays_coarse")
     return z, out
@@ -583,30 +563,18 @@ def _render_args(rays, S, N, packed_c, packed_f, use_disp, perturb, perturb_rand
     if N > 0:
         bufs.update(z_fine=torch.empty(B, S + N, **f32), raw_fine=torch.empty(B, S + N, 4, **f32), rgb_fine=torch.empty(B, 3, **f32),
                     depth_fine=torch.empty(B, **f32), opacity_fine=torch.empty(B, **f32))
-    if perturb > 0:
-        if perturb_rand is None:
-            raise ValueError("perturb>0 needs perturb_rand")
-        perturb_rand = _c(perturb_rand)
-        _check_draw("render", "perturb_rand", perturb_rand, B * S)
-    noise_c = None if noise_std == 0 else (_c(noise_c) if noise_c is not None else None)
-    noise_f = None if (noise_std == 0 or N == 0) else (_c(noise_f) if noise_f is not None else None)
+    perturb_rand = _perturb_arg("render", perturb, perturb_rand, B * S)
+    noise_c = _noise_arg("render", "noise_coarse", noise_c, noise_std, B * S)
+    noise_f = _noise_arg("render", "noise_fine", noise_f if N > 0 else None, noise_std, B * (S + N))
     if noise_std != 0 and (noise_c is None or (N > 0 and noise_f is None)):
         raise ValueError("render: noise_std != 0 needs the noise draws")
-    _check_draw("render", "noise_coarse", noise_c, B * S)
-    _check_draw("render", "noise_fine", noise_f, B * (S + N))
-    u_stride = 0
-    if u is not None and N > 0:
-        u = _c(u)
-        u_stride = N if u.dim() == 2 else 0
-        _check_draw("render", "u", u, B * N if u.dim() == 2 else N)
-    else:
-        u = None
+    u, u_stride = _u_arg("render", u if N > 0 else None, B, N)
     a.rays, a.B, a.S_c, a.N_i = rays.data_ptr(), B, int(S), int(N)
     a.packed_coarse = packed_c.data_ptr()
     a.packed_fine = packed_f.data_ptr() if packed_f is not None else None
     for k, t in bufs.items():
         setattr(a, k, t.data_ptr())
-    a.perturb_rand = perturb_rand.data_ptr() if perturb > 0 else None
+    a.perturb_rand = perturb_rand.data_ptr() if perturb_rand is not None else None
     a.perturb, a.use_disp = float(perturb), int(bool(use_disp))
     a.noise_coarse = noise_c.data_ptr() if noise_c is not None else None
     a.noise_fine = noise_f.data_ptr() if noise_f is not None else None
@@ -667,20 +635,26 @@ def render_train_fwd(rays, target, grad_scale, n_samples, n_importance, packed_c
 
 
 # ------------------------------------------------------------------------------- MLP backward (K2b)
-@device_guard
-def pack_weights_bwd(weights, biases, dtype, out=None):
-    """W^T A-fragment stream for the backward chain + the fp32 fold block (12 weights, 12 biases, state_dict order)."""
-    code = mlp_dtype_code(dtype)
-    keep = [_c(w.detach()) for w in weights]
-    keep_b = [_c(b.detach()) for b in biases]
-    for w in keep + keep_b:
-        require_gpu(w)
-    if out is None:
-        out = torch.empty(int(_lib.load().nerfhip_mlp_packed_bwd_bytes(code)), device=keep[0].device, dtype=torch.uint8)
-    wp = (ctypes.c_void_p * 12)(*[k.data_ptr() for k in keep])
-    bp = (ctypes.c_void_p * 12)(*[k.data_ptr() for k in keep_b])
-    check(_lib.load().nerfhip_mlp_pack_weights_bwd(wp, bp, ptr(out), code, stream_ptr()), "nerfhip_mlp_pack_weights_bwd")
-    return out
+FLAT_GRAD_FLOATS = sum(s[0] * s[1] + s[0] for s in PARAM_SHAPES)      # 595,844: a model's 24 gradients (16-byte multiple)
+
+
+def flat_grad_views(n_points, device, shapes=PARAM_SHAPES, out=None):
+    """One flat fp32 buffer for a model's 24 gradients + the 12 weight and 12 bias views of it (the layout FlatAdam mirrors).
+    out: the slice of a larger buffer to use as that flat buffer (mlp_bwd_multi: the models' buffers are consecutive slices of ONE
+    allocation, so that the gradients of a whole step are one contiguous message for the all-reduce).
+    n_points == 0: the C entry points launch nothing, so the gradients of an empty batch are explicit zeros."""
+    sizes = [s[0] * s[1] for s in shapes] + [s[0] for s in shapes]
+    if out is not None:
+        flat = out
+        if n_points == 0:
+            flat.zero_()
+    else:
+        flat = (torch.zeros if n_points == 0 else torch.empty)(sum(sizes), device=device, dtype=torch.float32)
+    views, off = [], 0
+    for sz in sizes:
+        views.append(flat[off:off + sz])
+        off += sz
+    return [v.view(s) for v, s in zip(views[:12], shapes)], views[12:], flat
 
 
 @device_guard
@@ -702,17 +676,9 @@ def mlp_bwd(g_out, out, packed_bwd, acts, dtype, shapes=PARAM_SHAPES, phases=7, 
         ws = torch.empty(int(lib.nerfhip_mlp_dw_workspace_bytes(n, code)), device=dev, dtype=torch.uint8)
         if workspace is not None:
             workspace["dys"], workspace["ws"] = dys, ws
-    # one flat fp32 buffer for all 24 gradients (595,844 floats): autograd adopts the views as p.grad,
-    # so a model's gradients are contiguous => ONE RCCL all-reduce per model, no flatten copies
-    sizes = [s[0] * s[1] for s in shapes] + [s[0] for s in shapes]
-    # n == 0: the C entry point launches nothing, so the gradients of an empty batch must be explicit zeros
-    flat = (torch.zeros if n == 0 else torch.empty)(sum(sizes), device=dev, dtype=torch.float32)
-    views, off = [], 0
-    for sz in sizes:
-        views.append(flat[off:off + sz])
-        off += sz
-    gw = [v.view(s) for v, s in zip(views[:12], shapes)]
-    gb = views[12:]
+    # one flat fp32 buffer for all 24 gradients: autograd adopts the views as p.grad, so a model's gradients are contiguous
+    # => ONE RCCL all-reduce per model, no flatten copies
+    gw, gb, flat = flat_grad_views(n, dev, shapes)
     gwp = (ctypes.c_void_p * 12)(*[t.data_ptr() for t in gw])
     gbp = (ctypes.c_void_p * 12)(*[t.data_ptr() for t in gb])
     check(lib.nerfhip_mlp_bwd_phases(ptr(g_out), ptr(out), n, ptr(packed_bwd), ptr(acts), ptr(dys), ptr(ws), gwp, gbp, 0, code,
@@ -743,7 +709,7 @@ def pack_tables(models, dtype):
     tabs, bufs = [], []
     for m in models:
         if not m.is_default_arch():
-            raise NotImplementedError("the fused HIP MLP implements the reference's default architecture only")
+            raise NotImplementedError(DEFAULT_ARCH_ONLY)
         wp, bp, dev = m._pack_args()
         tabs.append((wp, bp))
         bufs.append(m.train_buffers(dtype, dev))
@@ -770,27 +736,6 @@ def pack_models_train(models, dtype):
               "nerfhip_mlp_pack_weights_train_multi")
     mark_packed(models)
     return bufs
-
-
-FLAT_GRAD_FLOATS = sum(s[0] * s[1] + s[0] for s in PARAM_SHAPES)      # 595,844: a model's 24 gradients (16-byte multiple)
-
-
-def flat_grad_views(n_points, device, shapes=PARAM_SHAPES, out=None):
-    """One flat fp32 buffer for a model's 24 gradients + the 12 weight and 12 bias views of it (the layout FlatAdam mirrors).
-    out: the slice of a larger buffer to use as that flat buffer (mlp_bwd_multi: the models' buffers are consecutive slices of ONE
-    allocation, so that the gradients of a whole step are one contiguous message for the all-reduce)."""
-    sizes = [s[0] * s[1] for s in shapes] + [s[0] for s in shapes]
-    if out is not None:
-        flat = out
-        if n_points == 0:
-            flat.zero_()
-    else:
-        flat = (torch.zeros if n_points == 0 else torch.empty)(sum(sizes), device=device, dtype=torch.float32)
-    views, off = [], 0
-    for sz in sizes:
-        views.append(flat[off:off + sz])
-        off += sz
-    return [v.view(s) for v, s in zip(views[:12], shapes)], views[12:], flat
 
 
 def mlp_bwd_multi(entries, dtype, adam=None, phases=7, workspace=None, g_scale=None):

@@ -214,3 +214,59 @@ def test_render_shapes_and_refusals(dev):
     with torch.no_grad():
         out = rendering.render_rays(ms, _[0:2], O.make_rays(3, 10, "blender").to(dev), 64, False, 0, 0, 64, 32768, True)
     assert out["rgb_fine"].shape == (10, 3)
+
+
+def test_shared_argument_rules_reject_through_every_operator(dev, monkeypatch):
+    """The size rules of the caller-supplied draws (u, the noise, perturb_rand) and the raw (B,S,4) / target (B,3) check live in
+    one helper each (nerf_pl_amd/ops.py); every operator that takes such an argument rejects a wrong one with ValueError BEFORE
+    its launch — a wrong size would be an out-of-bounds device read, not an error.  Nothing is launched here: the library handle
+    is out of reach for the duration, so a call that got past its checks would fail the test instead of reading device memory."""
+    from nerf_pl_amd import _lib, ops
+
+    def no_launch():
+        raise AssertionError("an operator accepted a bad argument and went on to its launch")
+    monkeypatch.setattr(_lib, "load", no_launch)
+    B, S, N = 4, 8, 6
+    z = lambda *sh: torch.zeros(*sh, device=dev)
+    rays, zc, wc, raw, tgt, pk = z(B, 8), z(B, S), z(B, S), z(B, S, 4), z(B, 3), torch.zeros(16, device=dev, dtype=torch.uint8)
+    pr, nc, nf, u = z(B, S), z(B, S), z(B, S + N), z(B, N)
+
+    def render_fwd(**kw):
+        a = dict(perturb=1.0, perturb_rand=pr, noise_coarse=nc, noise_fine=nf, noise_std=1.0, u=u)
+        a.update(kw)
+        return ops.render_fwd(rays, S, N, pk, pk, "bf16", **a)
+
+    def render_train_fwd(**kw):
+        a = dict(perturb=1.0, perturb_rand=pr, noise_coarse=nc, noise_fine=nf, noise_std=1.0, u=u)
+        a.update(kw)
+        return ops.render_train_fwd(rays, tgt, 1.0, S, N, pk, pk, "bf16", pk, pk, **a)
+    calls = []
+    # u: None, (N,) or (B,N)
+    for bad in (z(B, N + 1), z(N + 1), z(B * N), z(1, N), z(N, B)):
+        calls += [lambda bad=bad: ops.sample_pdf_u(z(B, S + 1), wc, N, u=bad),
+                  lambda bad=bad: ops.fine_z(zc, wc, N, u=bad),
+                  lambda bad=bad: ops.composite_train_fine_z(raw, zc, rays, None, 0.0, True, tgt, 1.0, N, u=bad),
+                  lambda bad=bad: render_fwd(u=bad), lambda bad=bad: render_train_fwd(u=bad)]
+    # noise: B*S draws of the pass, read when noise_std != 0
+    for bad in (z(B, S + 1), z(B, S - 1), z(S)):
+        calls += [lambda bad=bad: ops.composite_train(raw, zc, rays, bad, 1.0, True, tgt, 1.0),
+                  lambda bad=bad: ops.composite_train_fine_z(raw, zc, rays, bad, 1.0, True, tgt, 1.0, N, u=u),
+                  lambda bad=bad: ops.composite_train_loss(raw, zc, rays, bad, 1.0, True, tgt, 1.0),
+                  lambda bad=bad: render_fwd(noise_coarse=bad), lambda bad=bad: render_train_fwd(noise_coarse=bad),
+                  lambda bad=bad: render_fwd(noise_fine=bad), lambda bad=bad: render_train_fwd(noise_fine=bad)]
+    calls += [lambda: render_fwd(noise_coarse=None), lambda: render_train_fwd(noise_fine=None)]
+    # perturb_rand: B*S draws, needed when perturb > 0
+    for bad in (None, z(B, S + 1), z(B, S - 1), z(S)):
+        calls += [lambda bad=bad: ops.sample_coarse_z(rays, S, False, 1.0, bad),
+                  lambda bad=bad: ops.mlp_fwd_rays_coarse(rays, S, pk, False, "bf16", False, 1.0, bad),
+                  lambda bad=bad: render_fwd(perturb_rand=bad), lambda bad=bad: render_train_fwd(perturb_rand=bad)]
+    # raw (B,S,4), target (B,3)
+    for bad_raw, bad_tgt in ((z(B, S, 3), tgt), (z(B, S), tgt), (raw, z(B, 4)), (raw, z(B))):
+        calls += [lambda r=bad_raw, t=bad_tgt: ops.composite_train(r, zc, rays, None, 0.0, True, t, 1.0),
+                  lambda r=bad_raw, t=bad_tgt: ops.composite_train_fine_z(r, zc, rays, None, 0.0, True, t, 1.0, N),
+                  lambda r=bad_raw, t=bad_tgt: ops.composite_train_loss(r, zc, rays, None, 0.0, True, t, 1.0)]
+    calls += [lambda: ops.composite_train_loss(raw, zc, rays, None, 0.0, True, tgt, 1.0, rgb_coarse=z(B, 4))]
+    for call in calls:
+        with pytest.raises(ValueError):
+            call()
+

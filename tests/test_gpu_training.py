@@ -769,6 +769,19 @@ def test_final_layer_fold_nobody_reads_f_or_its_gradient(dev, dtype):
     assert torch.equal(flat2, ref)
 
 
+def test_mlp_bwd_returns_the_flat_grad_views_layout(dev):
+    """ops.mlp_bwd's 24 gradients are ops.flat_grad_views' views of its flat buffer: PARAM_SHAPES, consecutive storage offsets,
+    595,844 floats (tests/test_layout_host.py checks the same function on the host) — and they are what the kernels wrote."""
+    from tests.test_layout_host import _check_flat_layout
+    ops, m, _, acts, raw, g_out = _fold_case(dev, "bf16", n=256)
+    gw, gb, flat = ops.mlp_bwd(g_out, raw, m.packed_weights_bwd("bf16"), acts, "bf16")
+    _check_flat_layout(ops, gw, gb, flat)
+    want_w, want_b, want_flat = ops.flat_grad_views(256, dev)
+    assert flat.device == want_flat.device and flat.dtype == torch.float32
+    assert [g.storage_offset() for g in gw + gb] == [g.storage_offset() for g in want_w + want_b]
+    assert torch.isfinite(flat).all() and float(flat.abs().max()) > 0 and torch.equal(torch.cat([g.flatten() for g in gw + gb]), flat)
+
+
 def test_final_layer_fold_equals_the_direct_products_fp32(dev):
     """dW_dir[:, :256] = sum_p dY_dir f^T, dW_final = sum_p (W_dx^T dY_dir) h8^T, db_final = sum_p W_dx^T dY_dir in float64 from the
     oracle's own activations, against what the dir job's G and mlp_bwd_fold_kernel produce (fp32 path): the same sums,
