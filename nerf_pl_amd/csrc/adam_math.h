@@ -1,6 +1,6 @@
 // The Adam update of torch.optim.Adam (non-amsgrad, L2 weight decay folded into the gradient; reference
 // utils/__init__.py:18-20), shared by adam_kernel (optim.hip) and the reduce kernel that applies it in place
-// (mlp_bwd.hip) so that both produce the same bits:
+// (mlp_bwd_reduce.hip) so that both produce the same bits:
 //     g  = grad + wd * p;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g g
 //     p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 #pragma once

@@ -1,25 +1,13 @@
 // fp8 (OCP e4m3, block-scaled) storage of the tensors saved for the weight-gradient GEMM — shared by the activation-saving
-// forward (mlp_fwd_kernel.h) and the backward chain (mlp_bwd.hip).  Format: mlp_layout.h "fp8 storage of the saved tensors".
+// forward (mlp_fwd_kernel.h) and the backward chain (mlp_bwd_chain.hip).  Format: mlp_layout.h "fp8 storage of the saved tensors".
 #pragma once
-#include "common.h"
-#include "mlp_layout.h"
+#include "mlp_device.h"
 
-#ifndef NERFHIP_STORE_AUX
-#define NERFHIP_STORE_AUX 2     // cache-policy bits of the write-once stores: 2 = nt
-#endif
 #ifndef NERFHIP_F8EXP
 #define NERFHIP_F8EXP 0         // timing experiments only (results invalid): 1 = convert but do not store, 2 = store without converting
 #endif
 
-#ifndef NERFHIP_STORE_SLACK
-#define NERFHIP_STORE_SLACK 1   // weight-ring boundaries let the stores of the last TWO chunk intervals stay in flight (0: one)
-#endif
-
 namespace nerfhip {
-using namespace mlp;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 // ---- training, fp8 storage (NERFHIP_BF16_F8, mlp_layout.h "fp8 storage of the saved tensors") -------------------------
 // max over the wave of a non-negative fp32 bit pattern (as unsigned): 6 DPP steps, result in an SGPR
@@ -44,11 +32,9 @@ __device__ __forceinline__ int f8_scale_byte(unsigned maxbits) {
     const int e = (int)((maxbits >> 23) & 0xffu) - 7;
     return e < 1 ? 1 : e;
 }
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
 // 8 bf16 (one slab of one lane) -> 8 e4m3 bytes (2 dwords), x / scale, round to nearest even
 __device__ __forceinline__ void slab_to_f8(const bf16x8& s, float scale, unsigned& d0, unsigned& d1) {
-    union { bf16x8 v; bf16x2v p[4]; } u;
+    union { bf16x8 v; bf16x2 p[4]; } u;
     u.v = s;
     union { s16x2 h; unsigned w; } a, b;
     a.w = 0u;
@@ -91,7 +77,7 @@ __device__ __forceinline__ int bf8_scale_byte(unsigned maxbits) {     // |x| / 2
     return e < 1 ? 1 : e;
 }
 __device__ __forceinline__ void slab_to_bf8(const bf16x8& s, float scale, unsigned& d0, unsigned& d1) {
-    union { bf16x8 v; bf16x2v p[4]; } u;
+    union { bf16x8 v; bf16x2 p[4]; } u;
     u.v = s;
     union { s16x2 h; unsigned w; } a, b;
     a.w = 0u;

@@ -19,15 +19,10 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "mlp_device.h"
 
 namespace nerfhip {
 namespace lin {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int kTileI = 128;  // output tile: 128 rows (i) x 128 or 256 columns (j); every wave a 64 x 64 sub-tile (2 x 2 MFMA blocks)
 constexpr int kStage = 32;   // reduction steps per LDS stage

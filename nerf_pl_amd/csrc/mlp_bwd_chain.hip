@@ -2,53 +2,19 @@
 // train.py:103-117 `loss.backward()`): per 32-point wave tile, the same register-resident chain as the forward, run in reverse
 // with W^T streamed through the LDS ring:  g_h(l-1) = W_l^T g_a(l),  g_a = g_h * relu'(h)  (gates read from the words the
 // forward saved).  Emits every dL/d(pre-activation) as slabs in the forward's fragment order for the weight-gradient GEMM
-// (mlp_bwd.hip).  MFMA-bound, ~0.93x the forward's MFMA count.
+// (mlp_bwd_dw.hip, mlp_bwd_dw_f8.hip).  MFMA-bound, ~0.93x the forward's MFMA count.
 // Its own translation unit: built with -amdgpu-sched-strategy=max-memory-clause (nerf_pl_amd/build.py), under which the
 // fp8-storage variant fits the 256-register budget of its 2-waves-per-SIMD launch bounds without spilling.
-#include <type_traits>
-
-#include "common.h"
-#include "mlp_layout.h"
+#include "mlp_device.h"
 #include "f8_store.h"
 #include "mlp_bwd_chain.h"
 
-#ifndef NERFHIP_STORE_AUX
-#define NERFHIP_STORE_AUX 2  // cache-policy bits of the dY stores: 2 = nt (-7 %; whole training step 1.65 -> 1.51 ms)
-#endif
 #ifndef NERFHIP_CHAIN_PK_GATE
 #define NERFHIP_CHAIN_PK_GATE 1   // bf16 chain: ReLU gates applied to the PACKED bf16 pairs (3 packed ops per pair instead of 2 per value)
 #endif
-#ifndef NERFHIP_DMA_SADDR
-#define NERFHIP_DMA_SADDR 1       // weight-stream DMAs address as SGPR base + one constant per-lane VGPR offset (no per-piece VALU address)
-#endif
 
 namespace nerfhip {
-using namespace mlp;
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-template <int PREC> struct BwdTraits;
-template <> struct BwdTraits<NERFHIP_BF16> {
-    using Slab = bf16x8;
-    static constexpr int NW = 8, WPS = 2;
-};
-template <> struct BwdTraits<NERFHIP_F32> {
-    using Slab = f32x8;
-    static constexpr int NW = 4, WPS = 1;
-};
-
-__device__ __forceinline__ void mk_slab(bf16x8& s, const float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = (__bf16)v[j];
-}
-__device__ __forceinline__ void mk_slab(f32x8& s, const float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = v[j];
-}
 __device__ __forceinline__ float slab_absmax8(const bf16x8& s) {
     float m = 0.0f;
 #pragma unroll
@@ -56,24 +22,6 @@ __device__ __forceinline__ float slab_absmax8(const bf16x8& s) {
     return m;
 }
 __device__ __forceinline__ float slab_absmax8(const f32x8& s) { return 0.0f; }   // (fp8 storage is bf16-only; keeps templates uniform)
-
-__device__ __forceinline__ void glds16b(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-// 16 bytes per lane, global -> LDS, source = wave-uniform base (SGPR pair) + per-lane byte offset `voff`
-__device__ __forceinline__ void glds16b_s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds_dst)
-        : "memory");
-}
 
 // ================================================================================================
 // Phase A: backward chain
@@ -92,64 +40,8 @@ __device__ __forceinline__ void glds16b_s(const void* sbase, unsigned voff, unsi
 #ifndef NERFHIP_CHAIN_DEPTH_F8
 #define NERFHIP_CHAIN_DEPTH_F8 0
 #endif
-template <int PREC>
-struct BwdStream {
-    static constexpr int NW = BwdTraits<PREC>::NW;
-    static constexpr int LPW = kChunkPieces / NW;
-    static constexpr int NCH = bwd_chunks(PREC);
-    const uint8_t* gsrc;       // packed stream + lane * 16 (per-lane address) | NERFHIP_DMA_SADDR: the stream itself (wave-uniform)
-    unsigned voff;             // NERFHIP_DMA_SADDR: lane * 16
-    unsigned lds_base;
-    int wave;
-    int pending;   // stores issued since the last boundary (constant-folded; see mlp_fwd.hip)
-    int pending_prev;
-#if NERFHIP_STREAM_PROBE
-    unsigned pr_wait = 0, pr_bar = 0, pr_n = 0;
-#endif
-
-    __device__ __forceinline__ void issue_chunk(int c) const {
-#pragma unroll
-        for (int i = 0; i < LPW; ++i) {
-            const int piece = wave + i * NW;
-#if NERFHIP_DMA_SADDR
-            glds16b_s(gsrc + ((size_t)c * kChunkPieces + piece) * kPieceBytes, voff,
-                      lds_base + (unsigned)((c % kSlots) * kChunkBytes + piece * kPieceBytes));
-#else
-            glds16b(gsrc + ((size_t)c * kChunkPieces + piece) * kPieceBytes,
-                    lds_base + (unsigned)((c % kSlots) * kChunkBytes + piece * kPieceBytes));
-#endif
-        }
-    }
-    __device__ __forceinline__ void boundary(int c) {
-        // chunk c's DMAs were issued at boundary c-2: younger than them are the stores of the interval before the previous
-        // boundary (pending_prev), chunk c+1's DMAs and the stores since the previous boundary => stores get two chunk
-        // intervals to retire before a boundary waits for them
-        const int n = (c + 1 < NCH ? LPW : 0) + pending + (NERFHIP_STORE_SLACK ? pending_prev : 0);
-        pending_prev = pending;
-        pending = 0;
-#if NERFHIP_STREAM_PROBE
-#define NH_WBAR
-        const unsigned t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
-#else
-#define NH_WBAR "\n\ts_barrier"
-#endif
-#define NH_WB(N) case N: asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" NH_WBAR ::: "memory"); break;
-        switch (n < 0 ? 0 : (n > 48 ? 48 : (n <= 8 ? n : (n & ~3)))) {
-            NH_WB(0) NH_WB(1) NH_WB(2) NH_WB(3) NH_WB(4) NH_WB(5) NH_WB(6) NH_WB(7) NH_WB(8)
-            NH_WB(12) NH_WB(16) NH_WB(20) NH_WB(24) NH_WB(28) NH_WB(32) NH_WB(36) NH_WB(40) NH_WB(44) NH_WB(48)
-            default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" NH_WBAR ::: "memory"); break;
-        }
-#undef NH_WB
-#undef NH_WBAR
-#if NERFHIP_STREAM_PROBE
-        const unsigned t1 = (unsigned)__builtin_amdgcn_s_memrealtime();
-        asm volatile("s_barrier" ::: "memory");
-        const unsigned t2 = (unsigned)__builtin_amdgcn_s_memrealtime();
-        pr_wait += t1 - t0; pr_bar += t2 - t1; pr_n += 1;
-#endif
-        if (c + 2 < NCH) issue_chunk(c + 2);
-    }
-};
+// the W^T stream's ring (mlp_device.h): the chain stores dY all along, so its boundaries always count stores
+template <int PREC> using BwdStream = RingStream<PrecTraits<PREC>::NW, bwd_chunks(PREC), true>;
 
 template <typename Slab>
 __device__ __forceinline__ Slab load_slab(__amdgpu_buffer_rsrc_t rsrc, int sec, int lane) {
@@ -162,16 +54,10 @@ __device__ __forceinline__ Slab load_slab(__amdgpu_buffer_rsrc_t rsrc, int sec, 
     return s;
 }
 template <int PREC, typename Slab>
-__device__ __forceinline__ void store_slab(BwdStream<PREC>& st, __amdgpu_buffer_rsrc_t rsrc, int sec, const Slab& s, int lane) {
-    const u32x4* src = reinterpret_cast<const u32x4*>(&s);
+__device__ __forceinline__ void store_slab(int& pending, __amdgpu_buffer_rsrc_t rsrc, int sec, const Slab& s, int lane) {
     const unsigned voff = (unsigned)lane * (unsigned)sizeof(Slab);
     const unsigned soff = (unsigned)(sec * 64 * sizeof(Slab) * act_il(PREC));        // (slab modes only: pieces IL KiB apart, mlp_layout.h)
-#pragma unroll
-    for (int q = 0; q < (int)(sizeof(Slab) / 16); ++q) {
-        // soffset must stay 0 (offset folded into VOFFSET): gfx950 store-data hazard, see mlp_fwd.hip save_slabs
-        __builtin_amdgcn_raw_buffer_store_b128(src[q], rsrc, voff + soff + 16 * q, 0, NERFHIP_STORE_AUX);
-        st.pending += 1;
-    }
+    store_slab_b128(pending, rsrc, s, voff + soff);      // (the section offset in VOFFSET, soffset 0: mlp_device.h)
 }
 
 // dY pair store / block scale in the configured 8-bit format (f8_store.h: e5m2 by default, see NERFHIP_F8_DY_E5M2)
@@ -198,14 +84,6 @@ __device__ __forceinline__ unsigned gate_mask(unsigned word) {
     unsigned m;
     asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(m) : "v"(word), "n"(BIT));
     return m;
-}
-
-template <int B, int E, typename F>
-__device__ __forceinline__ void bwd_static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        bwd_static_for<B + 1, E>(f);
-    }
 }
 
 // ---- one backward layer, OUTPUT-TILE-MAJOR: for each 32-row tile t of g_h(l-1) = W_l^T g_a(l):
@@ -260,15 +138,15 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
         return *reinterpret_cast<__attribute__((address_space(3))) const bf16x8*>(piece_ptr(g));
     };
     if constexpr (PREC == NERFHIP_BF16 && kChainDepth > 0) {
-        bwd_static_for<0, (kChainDepth < NFR ? kChainDepth : NFR)>([&](auto jc) { afr[decltype(jc)::value] = frag_read(jc); });
+        static_for<0, (kChainDepth < NFR ? kChainDepth : NFR)>([&](auto jc) { afr[decltype(jc)::value] = frag_read(jc); });
     }
-    bwd_static_for<0, NT>([&](auto tc) {
+    static_for<0, NT>([&](auto tc) {
         constexpr int t = decltype(tc)::value;
         f32x16& acc = acc2[t & 1];
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
         if constexpr (PREC == NERFHIP_BF16 && kChainDepth > 0) {
-            bwd_static_for<0, NKS>([&](auto kc) {
+            static_for<0, NKS>([&](auto kc) {
                 constexpr int ks = decltype(kc)::value;
                 constexpr int i = t * NKS + ks;
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[i % (kChainDepth > 0 ? kChainDepth : 1)], bslab(ks), acc, 0, 0, 0);
@@ -310,7 +188,7 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
             // (half << k) >> 15 (arithmetic) is 0xffff / 0 per half: shift, shift, and = 3 packed operations per pair (2 per
             // VALUE before).  The running maximum is taken over the UNGATED values (one v_max3 per pair): a valid, at most
             // slightly looser bound for the section's scale.
-            bwd_static_for<0, 8>([&](auto pc) {
+            static_for<0, 8>([&](auto pc) {
                 constexpr int p = decltype(pc)::value;               // pair p: values r = 2p, 2p + 1 -> slab 2t + (p >> 2), dword p & 3
                 constexpr int idx = 8 * (2 * t) + 2 * p;
                 typedef __attribute__((ext_vector_type(2))) float f32x2v;
@@ -333,7 +211,7 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
 #endif
         {
         float v[16];
-        bwd_static_for<0, 16>([&](auto rc) {
+        static_for<0, 16>([&](auto rc) {
             constexpr int r = decltype(rc)::value;           // slab 2t + (r >> 3), slot r & 7
             constexpr int idx = 8 * (2 * t) + r;
             const float gv = acc[r];
@@ -346,12 +224,12 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
             float v8[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v8[j] = v[8 * sl + j];
-            mk_slab(out[2 * t + sl], v8);
+            make_slab(out[2 * t + sl], v8);
         }
         }
         if constexpr (!F8) {
             // per-layer descriptor: the (possibly runtime, wave-uniform) section offset sits in its SALU-computed base, the
-            // per-tile offsets are immediates (soffset stays 0: gfx950 store-data hazard, see store_slab)
+            // per-tile offsets are immediates (soffset stays 0: gfx950 store-data hazard, mlp_device.h store_slab_b128)
             __amdgpu_buffer_rsrc_t dys_l = __builtin_amdgcn_make_buffer_rsrc(dy_tile + (size_t)dy_sec * 64 * sizeof(Slab) * act_il(PREC), 0,
                                                                               (int)(2 * NT * 64 * sizeof(Slab) * act_il(PREC)), 0x00020000);
             // NERFHIP_CHAIN_BURST slabs per run of back-to-back stores (2 = each tile's pair as soon as it is gated; the slabs of a
@@ -360,7 +238,7 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
             if constexpr ((t + 1) % TB == 0 || t == NT - 1) {
                 constexpr int t0 = (t / TB) * TB;
 #pragma unroll
-                for (int sl = 2 * t0; sl < 2 * t + 2; ++sl) store_slab(st, dys_l, sl, out[sl], lane);
+                for (int sl = 2 * t0; sl < 2 * t + 2; ++sl) store_slab<PREC>(st.pending, dys_l, sl, out[sl], lane);
             }
         }
     });
@@ -373,7 +251,7 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
 }
 
 template <int PREC, bool F8>
-__global__ __launch_bounds__(BwdTraits<PREC>::NW * 64, BwdTraits<PREC>::WPS)
+__global__ __launch_bounds__(PrecTraits<PREC>::NW * 64, PrecTraits<PREC>::WPS)
 void mlp_bwd_chain_kernel(BwdChainArgs A, const float* __restrict__ g_scale) {
     // ONE launch runs the chains of up to two models (a training step's fine and coarse network): the first A.blocks0 workgroups
     // belong to model 0, the rest to model 1 — wave-uniform selects of the per-model pointers, nothing else changes
@@ -386,11 +264,11 @@ void mlp_bwd_chain_kernel(BwdChainArgs A, const float* __restrict__ g_scale) {
     const uint8_t* __restrict__ acts_base = mdl ? A.acts[1] : A.acts[0];
     uint8_t* __restrict__ dys_base = mdl ? A.dys[1] : A.dys[0];
     static_assert(!F8 || PREC == NERFHIP_BF16, "fp8 storage is a bf16-compute mode");
-    using Slab = typename BwdTraits<PREC>::Slab;
+    using Slab = typename PrecTraits<PREC>::Slab;
     constexpr int kActTile = F8 ? f8_act_tile_bytes() : act_tile_bytes(PREC);
     constexpr int kGateOff = F8 ? f8_act_gate_off() : act_mask_off(PREC);
     constexpr int kDyTile = F8 ? f8_dy_tile_bytes() : kDySlabs * 64 * (int)sizeof(Slab);
-    constexpr int NW = BwdTraits<PREC>::NW;
+    constexpr int NW = PrecTraits<PREC>::NW;
     __shared__ __attribute__((aligned(1024))) char ring[kSlots * kChunkBytes + NW * 64 * (int)sizeof(Slab)];      // W^T ring | sigma-slab stash
 #if NERFHIP_STREAM_PROBE
     const uint64_t probe_t0 = __builtin_amdgcn_s_memrealtime();
@@ -446,16 +324,16 @@ void mlp_bwd_chain_kernel(BwdChainArgs A, const float* __restrict__ g_scale) {
     Slab zero_slab;
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = 0.0f;
-    mk_slab(zero_slab, v);
+    make_slab(zero_slab, v);
     Slab g_rgb, g_sig;
     {
         const float ga[3] = {g.x * o.x * (1.0f - o.x), g.y * o.y * (1.0f - o.y), g.z * o.z * (1.0f - o.z)};
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (h == 0 && j < 3) ? ga[j < 3 ? j : 0] : 0.0f;
-        mk_slab(g_rgb, v);
+        make_slab(g_rgb, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = (h == 0 && j == 0) ? g.w : 0.0f;
-        mk_slab(g_sig, v);
+        make_slab(g_sig, v);
     }
     if constexpr (F8) {
         if constexpr (PREC == NERFHIP_BF16) {
@@ -472,10 +350,10 @@ void mlp_bwd_chain_kernel(BwdChainArgs A, const float* __restrict__ g_scale) {
             save_scale_f8(st.pending, dy_tile, f8_dy_scale_off(), f8_dy_section(kDySigma), sb_sig, lane);
         }
     } else {
-        store_slab(st, dys, kDyRgb, g_rgb, lane);
-        store_slab(st, dys, kDyRgb + 1, zero_slab, lane);
-        store_slab(st, dys, kDySigma, g_sig, lane);
-        store_slab(st, dys, kDySigma + 1, zero_slab, lane);
+        store_slab<PREC>(st.pending, dys, kDyRgb, g_rgb, lane);
+        store_slab<PREC>(st.pending, dys, kDyRgb + 1, zero_slab, lane);
+        store_slab<PREC>(st.pending, dys, kDySigma, g_sig, lane);
+        store_slab<PREC>(st.pending, dys, kDySigma + 1, zero_slab, lane);
     }
 
     // scale bytes of the sections produced so far (F8); rgb / sigma pairs were stored above

@@ -6,16 +6,9 @@
 //     dx[:, 63:90] = W_dir[:, 256:283]^T dY_dir               (direction encoding enters dir_encoding, nerf.py:118)
 // one wave per 32-point tile, lane (n, h) holding the 128 features chain_feature(ks, h, j) of its point; the two halves are
 // combined with one cross-lane add per channel.  Weight rows are broadcast loads (two distinct addresses per instruction).
-#include <type_traits>
-
-#include "common.h"
-#include "mlp_layout.h"
+#include "mlp_device.h"
 
 namespace nerfhip {
-using namespace mlp;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
 
 template <typename Slab> __device__ __forceinline__ float sget(const Slab& s, int j) { return (float)s[j]; }
 
@@ -24,7 +17,7 @@ __global__ __launch_bounds__(256) void mlp_dx_embedded_kernel(const uint8_t* __r
                                                               const float* __restrict__ w1, const float* __restrict__ w5,
                                                               const float* __restrict__ wdir, float* __restrict__ gx,
                                                               int64_t gx_stride) {
-    using Slab = typename std::conditional<PREC == NERFHIP_BF16, bf16x8, f32x8>::type;
+    using Slab = typename PrecTraits<PREC>::Slab;
     const int lane = threadIdx.x & 63;
     const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= ntiles) return;

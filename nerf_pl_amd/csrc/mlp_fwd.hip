@@ -20,7 +20,7 @@ template <> int launch_fwd_variant<NERFHIP_BF16, 1, false, 2>(NH_ARGS);
 #undef NH_ARGS
 #undef NH_DECL
 
-// waves per workgroup of each variant (must match KCfg in mlp_fwd_kernel.h; checked there by static_assert)
+// waves per workgroup of each variant (must match PrecTraits in mlp_device.h; checked in mlp_fwd_variant.hip by static_assert)
 constexpr int fwd_waves(int prec, bool save) { return prec == NERFHIP_BF16 ? 8 : 4; }
 
 template <int PREC, int MODE>

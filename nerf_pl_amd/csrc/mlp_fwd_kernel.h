@@ -14,201 +14,23 @@
 //   bf16: v_mfma_f32_32x32x16_bf16, fp32 accumulate, 8 waves (2 per SIMD) = 256 points / workgroup
 //   fp32: v_mfma_f32_32x32x2_f32 (exact fp32 fma chain), 4 waves (1 per SIMD) = 128 points / workgroup
 #pragma once
-#include <type_traits>
-
-#include "common.h"
-#include "mlp_layout.h"
+#include "mlp_device.h"
 #include "f8_store.h"
 #include "sampling_math.h"
 
-#ifndef NERFHIP_STORE_AUX
-#define NERFHIP_STORE_AUX 2     // cache-policy bits of the activation stores: 2 = nt (written once, read by another kernel: -7 %)
-#endif
 #ifndef NERFHIP_FAST_SINCOS
 #define NERFHIP_FAST_SINCOS 1   // bf16 kernels only; the fp32 (parity) kernels always use sincosf
-#endif
-#ifndef NERFHIP_EXP
-#define NERFHIP_EXP 0
-#endif
-#ifndef NERFHIP_DMA_SADDR
-#define NERFHIP_DMA_SADDR 1     // weight-stream DMAs address as SGPR base + one constant per-lane VGPR offset (no per-piece VALU address)
 #endif
 #ifndef NERFHIP_PF2
 #define NERFHIP_PF2 2      // prefetch depth of the 2-waves-per-SIMD (256-register) bf16 kernels
 #endif
 
 namespace nerfhip {
-using namespace mlp;
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-template <int PREC> struct PrecTraits;
-template <> struct PrecTraits<NERFHIP_BF16> {
-    using Slab = bf16x8;                 // 8 input features of one point (4 VGPRs)
-};
-template <> struct PrecTraits<NERFHIP_F32> {
-    using Slab = f32x8;                  // 8 VGPRs
-};
-
-// Launch geometry.  bf16: 8 waves (2 per SIMD, 256 regs each) = 256 points / workgroup: the second wave of a SIMD
-// fills the matrix pipe while the first waits (LDS, chunk barrier) or issues its epilogue VALU.  fp32: 4 waves (1 per
-// SIMD, 512 regs; an fp32 slab set is 128 registers).  (Round 1 measured a 4-wave/512-register bf16 activation-saving
-// build as bimodal across MI355X boxes — 376 us on some, ~900 us on others, same binary — hence 8 waves everywhere.)
-template <int PREC, bool SAVE> struct KCfg {
-    static constexpr int NW = (PREC == NERFHIP_BF16) ? 8 : 4;
-    static constexpr int WPS = (PREC == NERFHIP_BF16) ? 2 : 1;
-};
-
-__device__ __forceinline__ void make_slab(bf16x8& s, const float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = (__bf16)v[j];
-}
-__device__ __forceinline__ void make_slab(f32x8& s, const float (&v)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = v[j];
-}
-
-// one 16-byte-per-lane global->LDS DMA; LDS destination = wave-uniform `lds_dst` + lane*16
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
-// the same with the source as wave-uniform base (SGPR pair) + per-lane byte offset `voff`
-__device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds_dst)
-        : "memory");
-}
-
-template <int PREC, int NCH, bool COUNT_STORES = false>
-struct WeightStream {
-    static constexpr int NW = KCfg<PREC, COUNT_STORES>::NW;    // COUNT_STORES == SAVE variant
-    static constexpr int LPW = kChunkPieces / NW;   // DMA instructions per wave per chunk
-    const uint8_t* gsrc;     // packed + lane*16 | NERFHIP_DMA_SADDR: packed (wave-uniform)
-    unsigned voff;           // NERFHIP_DMA_SADDR: lane*16
-    unsigned lds_base;       // LDS byte address of the ring
-    int wave;                // wave index in the workgroup (SGPR)
-    int pending;             // vector-memory STORE instructions issued since the last boundary (SAVE variant).
-                             // Straight-line code: the optimiser folds this to a constant at every boundary.
-    int pending_prev;        // ... and in the interval before that
-#if NERFHIP_STREAM_PROBE
-    unsigned pr_wait = 0, pr_bar = 0, pr_n = 0;     // 10 ns ticks at the boundaries' s_waitcnt / s_barrier, boundaries passed
-#endif
-
-    __device__ __forceinline__ void issue_piece(int c, int k) const {      // k-th of this wave's LPW pieces of chunk c
-        const int piece = wave + k * NW;
-#if NERFHIP_DMA_SADDR
-        glds16_s(gsrc + ((size_t)c * kChunkPieces + piece) * kPieceBytes, voff,
-                 lds_base + (unsigned)((c % kSlots) * kChunkBytes + piece * kPieceBytes));
-#else
-        glds16(gsrc + ((size_t)c * kChunkPieces + piece) * kPieceBytes,
-               lds_base + (unsigned)((c % kSlots) * kChunkBytes + piece * kPieceBytes));
-#endif
-    }
-    __device__ __forceinline__ void issue_chunk(int c) const {
-#pragma unroll
-        for (int i = 0; i < LPW; ++i) issue_piece(c, i);
-    }
-    // Called once for EVERY piece index G of the stream, in increasing order, right before piece G is read: the
-    // first piece of a chunk is the chunk boundary.  (Measured: spreading the LPW refill DMAs over the chunk and
-    // staggering them between the two halves of the workgroup — instead of one burst behind the barrier — is
-    // SLOWER: 203 vs 184 us forward, and 3x on the 4-wave SAVE variant; the burst stays.)
-    template <int G>
-    __device__ __forceinline__ void at_piece() {
-        if constexpr (G % kChunkPieces == 0) boundary(G / kChunkPieces);
-    }
-    // Called by every wave right before the first piece of chunk c is read.
-    __device__ __forceinline__ void boundary(int c) {
-#if NERFHIP_EXP == 1          // timing experiment only (results invalid): barriers kept, no refill DMAs after the prologue
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        return;
-#elif NERFHIP_EXP == 2        // timing experiment only: neither barriers nor refills (pure MFMA + LDS reads + epilogues)
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        return;
-#endif
-        // (1) my DMAs for chunk c have landed (chunk c+1's may stay in flight), my LDS reads of chunk c-1
-        // have returned; (2) barrier: same holds for every wave => chunk c is readable and the slot of
-        // chunk c-1 is free; (3) refill that slot with chunk c+2.
-        // vmcnt retires in issue order and counts stores too: the ops younger than chunk c's DMAs are the
-        // LPW DMAs of chunk c+1 plus the `pending` activation stores issued since the previous boundary
-        // (older stores are waited for as well — harmless).  Under-counting only over-waits.
-        if constexpr (COUNT_STORES) {
-            // chunk c's DMAs were issued at boundary c-2; younger than them are the stores of the interval before the previous
-            // boundary (pending_prev), chunk c+1's DMAs and the stores since the previous boundary (pending)
-            const int n = (c + 1 < NCH ? LPW : 0) + pending + (NERFHIP_STORE_SLACK ? pending_prev : 0);
-            pending_prev = pending;
-            pending = 0;
-#if NERFHIP_STREAM_PROBE
-            const unsigned t0 = (unsigned)__builtin_amdgcn_s_memrealtime();
-            wait_only(n);
-            const unsigned t1 = (unsigned)__builtin_amdgcn_s_memrealtime();
-            asm volatile("s_barrier" ::: "memory");
-            const unsigned t2 = (unsigned)__builtin_amdgcn_s_memrealtime();
-            pr_wait += t1 - t0; pr_bar += t2 - t1; pr_n += 1;
-#else
-            wait_barrier(n);
-#endif
-        } else if (c + 1 < NCH) {
-            if (LPW == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            else          asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        if (c + 2 < NCH) issue_chunk(c + 2);
-    }
-#if NERFHIP_STREAM_PROBE
-    static __device__ __forceinline__ void wait_only(int n) {
-#define NH_WB(N) case N: asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); break;
-        switch (n < 0 ? 0 : (n > 48 ? 48 : (n <= 8 ? n : (n & ~3)))) {
-            NH_WB(0) NH_WB(1) NH_WB(2) NH_WB(3) NH_WB(4) NH_WB(5) NH_WB(6) NH_WB(7) NH_WB(8)
-            NH_WB(12) NH_WB(16) NH_WB(20) NH_WB(24) NH_WB(28) NH_WB(32) NH_WB(36) NH_WB(40) NH_WB(44) NH_WB(48)
-            default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
-        }
-#undef NH_WB
-    }
-#endif
-    static __device__ __forceinline__ void wait_barrier(int n) {
-#define NH_WB(N) case N: asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-        switch (n < 0 ? 0 : (n > 48 ? 48 : (n <= 8 ? n : (n & ~3)))) {   // multiples of 4 above 8 (round DOWN = safe)
-            NH_WB(0) NH_WB(1) NH_WB(2) NH_WB(3) NH_WB(4) NH_WB(5) NH_WB(6) NH_WB(7) NH_WB(8)
-            NH_WB(12) NH_WB(16) NH_WB(20) NH_WB(24) NH_WB(28) NH_WB(32) NH_WB(36) NH_WB(40) NH_WB(44) NH_WB(48)
-            default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
-        }
-#undef NH_WB
-    }
-};
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E) — guarantees static register indexing
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
 
 // ---- training: save B-operand slabs in register (fragment) order, one coalesced 16-B store/lane/piece ----
-// Buffer stores through a per-wave descriptor with a 32-bit per-lane offset VGPR (no 64-bit address VGPR
-// pairs competing with the accumulators).  The section offset is added to the VOFFSET and soffset stays the
-// constant 0: with a wave-uniform soffset in an SGPR, LLVM's hazard recognizer assumes the ">64-bit store data
-// followed by a VALU write of the data VGPR" hazard cannot occur and lets the next VALU instruction overwrite
-// v[d:d+3] right behind the store — on gfx950 that corrupts lanes 12-15 of every 16 (measured: dY slabs with
-// 0x4000 patterns from the following v_and).  With soffset = 0 the compiler inserts the wait states.
-template <int PREC, int NCH, typename Slab, bool CS>
-__device__ __forceinline__ void save_slabs(WeightStream<PREC, NCH, CS>& st, uint8_t* tile_ptr, int sec,
-                                           const Slab* slabs, int n, int lane) {
+// (buffer stores with soffset 0: mlp_device.h store_slab_b128)
+template <int PREC, typename Slab>
+__device__ __forceinline__ void save_slabs(int& pending, uint8_t* tile_ptr, int sec, const Slab* slabs, int n, int lane) {
     constexpr int IL = act_il(PREC);        // (non-F8 callers only) piece pitch of the interleaved block, mlp_layout.h
     // One descriptor per call with the section offset folded into its (wave-uniform, SALU-computed) base: every store
     // then uses the SAME voffset VGPR (lane * sizeof(Slab)) and a small immediate.  (Folding the section offset into
@@ -218,14 +40,7 @@ __device__ __forceinline__ void save_slabs(WeightStream<PREC, NCH, CS>& st, uint
                                                                   (int)(n * 64 * sizeof(Slab) * IL), 0x00020000);
     const unsigned voff = (unsigned)lane * (unsigned)sizeof(Slab);
 #pragma unroll
-    for (int i = 0; i < n; ++i) {
-        const u32x4* src = reinterpret_cast<const u32x4*>(&slabs[i]);
-#pragma unroll
-        for (int q = 0; q < (int)(sizeof(Slab) / 16); ++q) {
-            __builtin_amdgcn_raw_buffer_store_b128(src[q], rs, voff + (unsigned)(i * 64 * sizeof(Slab) * IL) + 16 * q, 0, NERFHIP_STORE_AUX);
-            st.pending += 1;
-        }
-    }
+    for (int i = 0; i < n; ++i) store_slab_b128(pending, rs, slabs[i], voff + (unsigned)(i * 64 * sizeof(Slab) * IL));
 }
 
 // The lane id, recomputed (v_mbcnt): a value the register allocator can drop and recreate instead of keeping the prologue's
@@ -255,8 +70,6 @@ __device__ __forceinline__ int fresh_lane_opaque() {
 // Biases are read from a workgroup-shared 12 KiB LDS image filled once in the prologue (the in-stream bias pieces still
 // travel through the ring; they are not read), A fragments and encoding operands are prefetched D steps ahead ACROSS
 // layer boundaries (fragment slots are numbered over the whole network).
-typedef __attribute__((ext_vector_type(2))) short nh_s16x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 nh_bf16x2;
 
 NH_HD constexpr int layer_frags(int L) { return L < 0 ? 0 : kLayers[L].nt * (kLayers[L].enc_slabs + kLayers[L].chain_slabs); }
 NH_HD constexpr int frag_base(int L) {            // fragments before layer L (execution order)
@@ -333,12 +146,12 @@ __device__ __forceinline__ void epi_piece(Ctx& cx, St& st, const f32x16& c, Slab
         typedef __attribute__((ext_vector_type(2))) float f32x2v;
         typedef __attribute__((ext_vector_type(2))) unsigned short u16x2v;
         const f32x2v xv = {c[2 * p], c[2 * p + 1]};
-        nh_bf16x2 pk = __builtin_convertvector(xv, nh_bf16x2);       // one v_cvt_pk_bf16_f32
+        bf16x2 pk = __builtin_convertvector(xv, bf16x2);       // one v_cvt_pk_bf16_f32
         if (RELU) {     // relu after rounding == rounding after relu; packed signed-integer max with 0 clears negative halves
-            nh_s16x2 sv = __builtin_bit_cast(nh_s16x2, pk);
-            const nh_s16x2 z = {0, 0};
+            s16x2 sv = __builtin_bit_cast(s16x2, pk);
+            const s16x2 z = {0, 0};
             sv = __builtin_elementwise_max(sv, z);
-            pk = __builtin_bit_cast(nh_bf16x2, sv);
+            pk = __builtin_bit_cast(bf16x2, sv);
         }
         o[2 * (p & 3)] = pk[0];
         o[2 * (p & 3) + 1] = pk[1];
@@ -369,7 +182,7 @@ __device__ __forceinline__ void epi_piece(Ctx& cx, St& st, const f32x16& c, Slab
         if (!F8 && layer_out_saved(PL) && (p & 3) == 3) {
             const int si = 2 * pt + (p >> 2);
             if ((si + 1) % NERFHIP_SAVE_BURST == 0)
-                save_slabs(st, cx.tile, layer_out_sec(PL) + si + 1 - NERFHIP_SAVE_BURST, &po[si + 1 - NERFHIP_SAVE_BURST], NERFHIP_SAVE_BURST, lane);
+                save_slabs<PREC>(st.pending, cx.tile, layer_out_sec(PL) + si + 1 - NERFHIP_SAVE_BURST, &po[si + 1 - NERFHIP_SAVE_BURST], NERFHIP_SAVE_BURST, lane);
         }
         if (RELU && p == 7 && (pt & 1)) {
             __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(cx.gate_base + layer_gate_piece(PL) * kPieceBytes * act_il(PREC, F8), 0,
@@ -586,7 +399,7 @@ template <int PREC, bool SAVE> struct FwdLds {
     static constexpr int kBiasArea = kNumLayers * kPieceBytes;
     static constexpr int kRingOff = kBiasArea;
     static constexpr int kStashOff = kBiasArea + kSlots * kChunkBytes;
-    static constexpr int kBytes = kStashOff + KCfg<PREC, SAVE>::NW * kEncStash;
+    static constexpr int kBytes = kStashOff + PrecTraits<PREC>::NW * kEncStash;
 };
 
 // The whole network for the 32 * NW points of (virtual) workgroup `blk` — the body of mlp_fwd_kernel, and of every sub-pass of
@@ -599,7 +412,7 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
                                              float* __restrict__ out, uint8_t* __restrict__ save, const FwdZGen& zg) {
     using Slab = typename PrecTraits<PREC>::Slab;
     constexpr bool SAVE = SV != 0, F8 = SV == 2;
-    constexpr int NW = KCfg<PREC, SAVE>::NW;
+    constexpr int NW = PrecTraits<PREC>::NW;
     constexpr int NCH = SIGMA_ONLY ? chunks_upto_layer(kSigmaLayer + 1, PREC) : chunks_upto_layer(kNumLayers, PREC);
     constexpr int kEncStash = FwdLds<PREC, SAVE>::kEncStash;
     constexpr int kBiasArea = FwdLds<PREC, SAVE>::kBiasArea;
@@ -647,7 +460,7 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
         row = in0 + pc * aux;
     }
 
-    WeightStream<PREC, NCH, SAVE> st;
+    RingStream<NW, NCH, SAVE> st;
 #if NERFHIP_DMA_SADDR
     st.gsrc = packed;
 #else
@@ -713,8 +526,8 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
     } else if (SAVE) {
         // (wave-uniform) the bf16 step leaves the encoding slabs out: mlp_bwd_dw_kernel forms them again from (rays, z)
         if (!(PREC == NERFHIP_BF16 && MODE == MODE_RAYS && zg.skip_enc_save)) {
-            save_slabs(st, tile_base, kActEncX, encx, kXyzSlabs, lane);
-            save_slabs(st, tile_base, kActEncD, encd, kDirSlabs, lane);
+            save_slabs<PREC>(st.pending, tile_base, kActEncX, encx, kXyzSlabs, lane);
+            save_slabs<PREC>(st.pending, tile_base, kActEncD, encd, kDirSlabs, lane);
         }
     }
     char* enc_x = stash_area + wave * kEncStash;      // wave-uniform stash bases
@@ -834,7 +647,7 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
 }
 
 template <int PREC, int MODE, bool SIGMA_ONLY, int SV>
-__global__ __launch_bounds__((KCfg<PREC, (SV != 0)>::NW * 64), (KCfg<PREC, (SV != 0)>::WPS))
+__global__ __launch_bounds__(PrecTraits<PREC>::NW * 64, PrecTraits<PREC>::WPS)
 void mlp_fwd_kernel(const float* __restrict__ in0, const float* __restrict__ in1, int64_t n, int64_t aux,
                     const uint8_t* __restrict__ packed, float* __restrict__ out, uint8_t* __restrict__ save, FwdZGen zg) {
     __shared__ __attribute__((aligned(1024))) char lds_all[FwdLds<PREC, (SV != 0)>::kBytes];

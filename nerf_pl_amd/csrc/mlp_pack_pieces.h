@@ -3,8 +3,7 @@
 //   pack_bwd_piece: the backward chain's W^T stream, followed by the fp32 fold block (mlp_layout.h kFold*: W_f, W_dx, b_f as
 //                   mlp_bwd_fold_kernel reads them)
 #pragma once
-#include "common.h"
-#include "mlp_layout.h"
+#include "mlp_device.h"
 
 namespace nerfhip {
 
@@ -53,7 +52,6 @@ template <int PREC>
 __device__ __forceinline__ void pack_fold_tile(const ParamTable& P, uint8_t* __restrict__ packed, uint8_t* __restrict__ packed_bwd, int tile,
                                                float* lds) {
     using namespace mlp;
-    typedef __attribute__((ext_vector_type(16))) float f32x16;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int rt = tile >> 3, ct = tile & 7;
     const int r = lane & 31, kh = lane >> 5;
@@ -101,7 +99,6 @@ __device__ __forceinline__ void pack_fold_tile(const ParamTable& P, uint8_t* __r
     constexpr int PPF = ppf(PREC);
     auto emit = [&](uint8_t* img, int g0, const float (&v)[8]) {
         if (PREC == NERFHIP_BF16) {
-            typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
             bf16x8 pk;
 #pragma unroll
             for (int j = 0; j < 8; ++j) pk[j] = (__bf16)v[j];
@@ -182,7 +179,6 @@ __device__ __forceinline__ uint4 pack_fwd_piece(const ParamTable& P, int g, int 
                 v[j] = (row < ly.n_out && col >= 0) ? W[(size_t)row * ldw + col] : 0.0f;      // (folded pieces: never stored, see pack_fold_tile)
             }
             if (PREC == NERFHIP_BF16) {
-                typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
                 bf16x8 p;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) p[j] = (__bf16)v[j];     // round-to-nearest-even
@@ -229,7 +225,6 @@ __device__ __forceinline__ uint4 pack_bwd_piece(const ParamTable& P, int g, int 
             }
         }
         if (PREC == NERFHIP_BF16) {
-            typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
             bf16x8 p;
 #pragma unroll
             for (int j = 0; j < 8; ++j) p[j] = (__bf16)v[j];

@@ -27,7 +27,7 @@ static int render_tail_floats_host(int S_c, int N_i) {
 
 static bool render_shape_ok(int64_t B, int S_c, int N_i, int dtype) {
     if (dtype != NERFHIP_F32 && dtype != NERFHIP_BF16 && dtype != NERFHIP_BF16_F8) return false;
-    const int pts = 32 * (dtype == NERFHIP_F32 ? 4 : 8);          // points per sub-pass (KCfg::NW waves of 32)
+    const int pts = 32 * (dtype == NERFHIP_F32 ? 4 : 8);          // points per sub-pass (PrecTraits::NW waves of 32)
     if (B <= 0 || B % kRenderRays != 0 || B / kRenderRays > 0x7fffffff || S_c < 3 || N_i < 0) return false;
     if ((kRenderRays * S_c) % pts != 0 || (N_i > 0 && (kRenderRays * (S_c + N_i)) % pts != 0)) return false;
     if ((int64_t)B * (S_c + N_i) / pts > 0x7fffffff) return false;

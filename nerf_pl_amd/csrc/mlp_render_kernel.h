@@ -100,11 +100,11 @@ __device__ __forceinline__ void render_tail(const bool fine_pass, const bool wit
 }
 
 template <int PREC, int SV>
-__global__ __launch_bounds__((KCfg<PREC, (SV == 1 || SV == 2)>::NW * 64), (KCfg<PREC, (SV == 1 || SV == 2)>::WPS))
+__global__ __launch_bounds__(PrecTraits<PREC>::NW * 64, PrecTraits<PREC>::WPS)
 void mlp_render_kernel(const RenderArgs args_by_value) {          // (read through render_args(), never by name)
     constexpr bool TRAIN = SV == 1 || SV == 2, TT = SV == 3;
     constexpr int FSV = TT ? 0 : SV;                               // the network body's own variant
-    constexpr int NW = KCfg<PREC, TRAIN>::NW, PTS = 32 * NW, R = kRenderRays;
+    constexpr int NW = PrecTraits<PREC>::NW, PTS = 32 * NW, R = kRenderRays;
     __shared__ __attribute__((aligned(1024))) char lds_all[FwdLds<PREC, TRAIN>::kBytes];
     __shared__ float red[2][16];
     __shared__ unsigned last_s;

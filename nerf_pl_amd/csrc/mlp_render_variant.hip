@@ -11,7 +11,7 @@ namespace nerfhip {
 
 template <>
 int launch_render_variant<NH_PREC, NH_SV>(const RenderArgs& a, unsigned groups, hipStream_t stream) {
-    constexpr int NW = KCfg<NH_PREC, (NH_SV == 1 || NH_SV == 2)>::NW;
+    constexpr int NW = PrecTraits<NH_PREC>::NW;
     hipLaunchKernelGGL((mlp_render_kernel<NH_PREC, NH_SV>), dim3(groups), dim3(NW * 64), 0, stream, a);
     return nerfhip_launch_status();
 }

@@ -1,4 +1,4 @@
-"""CPU: the weight-gradient launch's split plan (host logic of csrc/mlp_bwd.hip `dw_plan`, exported as nerfhip_mlp_dw_plan).
+"""CPU: the weight-gradient launch's split plan (host logic of csrc/mlp_dw_plan.h `dw_plan`, exported as nerfhip_mlp_dw_plan).
 The launch computes dW_l = dY_l^T X_l for the 12 parameter tensors of each model (reference nerf.py:42-81 / autograd of
 nerf.py:100-124); a workgroup = (job, point range).  No compute calls: the plan is plain host arithmetic."""
 import ctypes
@@ -40,7 +40,7 @@ def test_benchmark_step_is_one_round_of_the_256_cus(lib):
 
 
 def iter_cost(kib):
-    """Round 6 cost model of one ring iteration of the bf16 kernel, in ns: 150 + 45 per KiB of its stage (csrc/mlp_bwd.hip
+    """Round 6 cost model of one ring iteration of the bf16 kernel, in ns: 150 + 45 per KiB of its stage (csrc/mlp_dw_plan.h
     NERFHIP_DW_COST_A/B; sweep in profiles/r06_dw_plan_cost_ab.txt).  Round 4's kernel measured 0.7-1.8 us per iteration
     (tools/dw_probe.py) and planned with 300 + 35 per KiB; the 2 x 4 wave split, dot2 bias sums and register-major epilogue of
     round 6 shrank the fixed part, and the sweep then preferred a plan nearer to bytes-proportional."""

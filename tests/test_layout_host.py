@@ -16,6 +16,17 @@ def test_layout_maps_are_consistent(tmp_path):
     assert r.returncode == 0 and "layout ok" in r.stdout, r.stdout + r.stderr
 
 
+def test_dw_plan_header_is_plain_host_code(tmp_path):
+    """nerf_pl_amd/csrc/mlp_dw_plan.h (the weight-gradient launch's split plan) compiles and links with g++ alone — csrc/ is the only
+    include path, no HIP header on it — and plans the benchmark step (fine 1024 x 192 + coarse 1024 x 64 points) as the library does
+    (tests/test_dw_plan.py): 256 workgroups with e4m3 storage, 256 in bf16, 512 in fp32."""
+    exe = str(tmp_path / "dw_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "nerf_pl_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "host", "dw_plan_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.split() == ["256", "256", "512"], r.stdout + r.stderr
+
+
 def test_ahead_of_step_weight_images_are_trusted_only_under_a_live_announcing_optimizer():
     """`_serial_tracked` used to be a flag FlatAdam set and nobody cleared.  It is a weak reference to the optimizer now (a
     model later stepped by something else is not vouched for by a dead FlatAdam), and load_state_dict — the reference's load_ckpt,
