@@ -329,6 +329,31 @@ int nerfhip_adam_step(float* const* params_host, const float* const* grads_host,
                       float* const* exp_avg_sq_host, const int64_t* numel_host, int n_tensors, float* state, float lr,
                       float beta1, float beta2, float eps, float weight_decay, nerfhip_stream_t stream);
 
+/* ---- N2b. RAdam and Ranger on the same flat storage  (utils/__init__.py:21-26 -> utils/optimizers.py:6-95 RAdam,
+ * :266-405 Ranger = RAdam + lookahead) ----
+ * Same conventions as nerfhip_adam_step: HOST arrays of `n_tensors` (<= 8) DEVICE pointers, the same 2-float DEVICE `state`
+ * {step count, arrival ticket} advanced by the launch itself, one launch for all tensors, nothing allocated or synchronised
+ * (capturable).  Hyper-parameters are doubles: the rectification term N_sma(t) and the step size are formed in double on the
+ * device, as the reference forms them in Python floats (fp32 cannot resolve N_sma(5) = 4.996 against RAdam's threshold 5).
+ * Weight decay is NOT folded into the gradient (p -= wd lr p), eps is added to sqrt(exp_avg_sq) directly; both moments are
+ * updated on every step.
+ *   RAdam  (optimizers.py:62-93): rectified update when N_sma >= 5; below it the momentum-only form when degenerated_to_sgd,
+ *          else the parameters (weight decay included) are left untouched.
+ *   Ranger (optimizers.py:369-403): rectified when N_sma > n_sma_threshold, momentum-only form otherwise; weight decay always;
+ *          when t % k == 0 the lookahead step slow += alpha (p - slow), p = slow follows.  `slow_host`: flat DEVICE tensors like
+ *          params.  The launch with t = 1 fills them from the parameters before it updates those (optimizers.py:353-354); other
+ *          launches neither read nor write them unless t % k == 0.
+ * NERFHIP_E_BADARG: null pointers, n_tensors outside 1..8, numel < 1, lr / eps / weight_decay < 0, a beta outside [0, 1),
+ * k < 1, alpha outside [0, 1].                                                                                          */
+int nerfhip_radam_step(float* const* params_host, const float* const* grads_host, float* const* exp_avg_host,
+                       float* const* exp_avg_sq_host, const int64_t* numel_host, int n_tensors, float* state, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, int degenerated_to_sgd,
+                       nerfhip_stream_t stream);
+int nerfhip_ranger_step(float* const* params_host, const float* const* grads_host, float* const* exp_avg_host,
+                        float* const* exp_avg_sq_host, const int64_t* numel_host, int n_tensors, float* state,
+                        float* const* slow_host, double alpha, int k, double n_sma_threshold, double lr, double beta1,
+                        double beta2, double eps, double weight_decay, nerfhip_stream_t stream);
+
 /* ---- N1. ray generation  (datasets/ray_utils.py:5-94; consumers blender.py:37-69, llff.py:236-253) --------
  * get_ray_directions: dirs (H,W,3) = ((i-W/2)/focal, -(j-H/2)/focal, -1), i = column, j = row.
  * get_rays: rays_d = normalise(directions @ c2w[:, :3].T), rays_o = c2w[:, 3]; c2w (3,4) row-major DEVICE array.

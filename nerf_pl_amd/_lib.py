@@ -19,6 +19,7 @@ _c_void_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
 _f32 = ctypes.c_float
+_f64 = ctypes.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/nerfhip.h exactly
 SIGNATURES = {
@@ -65,6 +66,11 @@ SIGNATURES = {
     "nerfhip_mlp_dx_embedded": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _int, _c_void_p],
     "nerfhip_adam_step": [ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
                           ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64), _int, _c_void_p, _f32, _f32, _f32, _f32, _f32, _c_void_p],
+    "nerfhip_radam_step": [ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
+                           ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64), _int, _c_void_p, _f64, _f64, _f64, _f64, _f64, _int, _c_void_p],
+    "nerfhip_ranger_step": [ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p),
+                            ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64), _int, _c_void_p, ctypes.POINTER(_c_void_p), _f64, _int,
+                            _f64, _f64, _f64, _f64, _f64, _f64, _c_void_p],
     "nerfhip_mlp_bwd": [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                         ctypes.POINTER(_c_void_p), ctypes.POINTER(_c_void_p), _int, _int, _c_void_p],
     "nerfhip_sample_batch": [_c_void_p, _c_void_p, _c_void_p, _i64, _int, _int, ctypes.c_double, _f32, _f32, _int, _f32, _c_void_p,

@@ -79,7 +79,8 @@ class NeRFSystem(_Base):
     def configure_optimizers(self):
         """get_optimizer + get_scheduler of the reference (utils/__init__.py:10-53), dispatched on the same hparams
         (`optimizer`, `momentum`, `weight_decay`, `lr_scheduler`, `num_epochs`, `poly_exp`, `decay_step`, `decay_gamma`).
-        Recipes this package does not implement raise instead of silently training with a different one."""
+        `radam` / `ranger` are optim.FlatRAdam / FlatRanger; `warmup_epochs` > 0 wraps the scheduler in
+        schedulers.GradualWarmupScheduler for `sgd` and `adam` only (utils/__init__.py:45-47)."""
         hp = self.hp
         eps = 1e-8
         params = [p for m in self.models for p in m.parameters()]
@@ -94,8 +95,10 @@ class NeRFSystem(_Base):
         elif name == 'sgd':
             self.optimizer = torch.optim.SGD(params, lr=hp.lr, momentum=getattr(hp, 'momentum', 0.9), weight_decay=wd)
         elif name in ('radam', 'ranger'):
-            raise NotImplementedError("optimizer %r (utils/optimizers.py of the reference) is outside the hot path this "
-                                      "package implements; use 'adam' or 'sgd'" % name)
+            # utils/optimizers.py of the reference, on flat storage with a device-resident step counter (HIP kernels; no CPU form:
+            # CPU parameters raise NerfHipError)
+            from .optim import FlatRAdam, FlatRanger
+            self.optimizer = (FlatRAdam if name == 'radam' else FlatRanger)(self.models, lr=hp.lr, eps=eps, weight_decay=wd)
         else:
             raise ValueError('optimizer not recognized!')
 
@@ -110,8 +113,10 @@ class NeRFSystem(_Base):
             scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimizer, lambda epoch: (1 - epoch / n_ep) ** pexp)
         else:
             raise ValueError('scheduler not recognized!')
-        if getattr(hp, 'warmup_epochs', 0) > 0:
-            raise NotImplementedError("warmup_epochs > 0 (utils/warmup_scheduler.py of the reference) is not implemented")
+        if getattr(hp, 'warmup_epochs', 0) > 0 and name not in ('radam', 'ranger'):       # ignored for those, as in the reference
+            from .schedulers import GradualWarmupScheduler
+            scheduler = GradualWarmupScheduler(self.optimizer, multiplier=getattr(hp, 'warmup_multiplier', 1.0),
+                                               total_epoch=hp.warmup_epochs, after_scheduler=scheduler)
         return [self.optimizer], [scheduler]
 
     def training_step(self, batch, batch_nb):
