@@ -542,6 +542,31 @@ int nerfhip_mesh_color_finish(const double* accum, int64_t V, uint8_t* out, nerf
 /* out (n) uint8 = trunc(float32(rgb * 255)): the vertex-normal mode's colours (extract_color_mesh.py:279)                  */
 int nerfhip_mesh_rgb_to_u8(const float* rgb, int64_t n, uint8_t* out, nerfhip_stream_t stream);
 
+/* ---- scene loading  (datasets/blender.py:47-58,90-95; nerf_pl_amd/datasets, DESIGN.md "Scene loading") -----------------------
+ * What the reference does per image on the host with PIL and torchvision, on byte images in HBM.  All three: n == 0 is success;
+ * null pointers with n > 0, sizes < 0 and unsupported channel counts are NERFHIP_E_BADARG before anything is launched.
+ *
+ * png_unfilter: reverses the PNG scanline filters 0-4 (None, Sub, Up, Average, Paeth; arithmetic modulo 256, Paeth ties a, b, c)
+ * of n_images inflated IDAT streams of equal size: 8-bit, non-interlaced, ch = 1 | 3 | 4, each H x (1 + W ch) bytes, back to
+ * back.  out (n_images,H,W,ch) uint8 (4-byte aligned when ch == 4).  error_flags (n_images) int32: written by the launch, nonzero
+ * where a scanline names a filter above 4 (such a line is copied as if unfiltered; no address depends on the filter byte).     */
+int nerfhip_png_unfilter(const uint8_t* streams, uint8_t* out, int32_t* error_flags, int n_images, int H, int W, int ch,
+                         nerfhip_stream_t stream);
+/* PIL.Image.resize((out_w, out_h), Image.LANCZOS) of n_images 8-bit RGBA images (n,in_h,in_w,4) -> (n,out_h,out_w,4), byte for
+ * byte: premultiply by alpha, a horizontal pass (when the width changes) into an 8-bit intermediate, a vertical pass (when the
+ * height changes), un-premultiply; equal sizes copy.  Per changed axis the caller supplies Pillow's taps as DEVICE int32 tables:
+ * xmin (out), count (out) and taps (out, ksize) in 22-bit fixed point (formed in double on the host:
+ * nerf_pl_amd.imageio_min.lanczos_taps).  A window reaching outside the input is clamped to it.  workspace: in_h * out_w * 4
+ * bytes per image, needed when both axes change (else NULL ok).  in / out / workspace 4-byte aligned and distinct.            */
+int nerfhip_resize_rgba_lanczos(const uint8_t* in, uint8_t* out, uint8_t* workspace, int n_images, int in_h, int in_w, int out_h,
+                                int out_w, const int32_t* xmin_h, const int32_t* count_h, const int32_t* taps_h, int ksize_h,
+                                const int32_t* xmin_v, const int32_t* count_v, const int32_t* taps_v, int ksize_v,
+                                nerfhip_stream_t stream);
+/* ToTensor + the blend onto white (blender.py:56-58,93): f = byte / 255 (fp32 division), rgb (n,3) = f_c * f_a + (1 - f_a) with
+ * the product, the difference and the sum rounded separately; valid_mask (n) uint8 = alpha > 0 (NULL ok).  rgba (n,4) uint8,
+ * 4-byte aligned; rgb may point into a larger (pixels,3) array, so a scene's colours are assembled in place.                  */
+int nerfhip_rgba_to_rgb_white(const uint8_t* rgba, float* rgb, uint8_t* valid_mask, int64_t n, nerfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,9 +30,10 @@ def default_mlp_dtype():
     return _DEFAULT_MLP_DTYPE
 
 
-def install():
+def install(datasets=False):
     """Register this package's modules under the names the reference imports
-    (train.py:10-11, eval.py:9-10, models/rendering.py:2)."""
+    (train.py:10-11, eval.py:9-10, models/rendering.py:2).  datasets=True: also `datasets` and `datasets.blender`
+    (train.py:8, eval.py:12) — off by default, so that inside a reference tree the reference's own loaders stay in charge."""
     from . import models, ops
     from .models import nerf, rendering
     sys.modules["models"] = models
@@ -41,3 +42,7 @@ def install():
     tss = types.ModuleType("torchsearchsorted")
     tss.searchsorted = ops.searchsorted
     sys.modules["torchsearchsorted"] = tss
+    if datasets:
+        from . import datasets as ds
+        sys.modules["datasets"] = ds
+        sys.modules["datasets.blender"] = ds.blender

@@ -125,6 +125,10 @@ SIGNATURES = {
     "nerfhip_mesh_color_accumulate": [_c_void_p, _c_void_p, _c_void_p, _i64, _f32, _c_void_p, _c_void_p],
     "nerfhip_mesh_color_finish": [_c_void_p, _i64, _c_void_p, _c_void_p],
     "nerfhip_mesh_rgb_to_u8": [_c_void_p, _i64, _c_void_p, _c_void_p],
+    "nerfhip_png_unfilter": [_c_void_p, _c_void_p, _c_void_p, _int, _int, _int, _int, _c_void_p],
+    "nerfhip_resize_rgba_lanczos": [_c_void_p, _c_void_p, _c_void_p, _int, _int, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p,
+                                    _int, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p],
+    "nerfhip_rgba_to_rgb_white": [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p],
 }
 
 

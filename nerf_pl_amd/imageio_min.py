@@ -1,6 +1,8 @@
 """Image / depth writers of the reference's eval loop (eval.py:119-149) without its imageio / cv2 dependencies:
 PNG (8-bit RGB or grey, zlib-deflated, filter 0), PFM (datasets/depth_utils.py:43-69 `save_pfm` / `read_pfm`, same bytes)
-and the raw little-endian float32 dump of `--depth_format bytes` (eval.py:135-137).  Host-side, numpy only."""
+and the raw little-endian float32 dump of `--depth_format bytes` (eval.py:135-137); and the host half of scene loading
+(nerf_pl_amd/datasets): the PNG container parser and Pillow's Lanczos taps.  Host-side, numpy only."""
+import math
 import re
 import struct
 import sys
@@ -60,6 +62,86 @@ def read_png(path):
         raise NotImplementedError("only filter 0 is decoded")
     out = raw[:, 1:].reshape(h, w, ch)
     return out[:, :, 0].copy() if ch == 1 else out.copy()
+
+
+def png_inflate(data):
+    """PNG file contents (bytes, or a path) -> (w, h, channels, inflated IDAT stream).  The stream is h scanlines of
+    1 filter byte + w * channels bytes, still filtered: the GPU reverses the filters (ops.decode_png_batch).  Only what that
+    kernel takes is accepted: 8 bits per sample, no interlace, grey / RGB / RGBA."""
+    if isinstance(data, str):
+        with open(data, "rb") as f:
+            data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("not a PNG file")
+    pos, idat, hdr = 8, [], None
+    while pos + 8 <= len(data):
+        n, tag = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if tag == b"IHDR":
+            hdr = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"IEND":
+            break
+        pos += 12 + n
+    if hdr is None:
+        raise ValueError("PNG without IHDR")
+    w, h, depth, color, _, _, interlace = hdr
+    if depth != 8:
+        raise ValueError("PNG bit depth %d is not supported (8 only)" % depth)
+    if interlace != 0:
+        raise ValueError("interlaced PNG is not supported")
+    if color not in (0, 2, 6):
+        raise ValueError("PNG colour type %d (%s) is not supported (grey, RGB, RGBA only)"
+                         % (color, {3: "palette", 4: "grey + alpha"}.get(color, "unknown")))
+    ch = {0: 1, 2: 3, 6: 4}[color]
+    raw = zlib.decompress(b"".join(idat))
+    if len(raw) != h * (1 + w * ch):
+        raise ValueError("PNG data holds %d bytes, %d x %d x %d needs %d" % (len(raw), h, w, ch, h * (1 + w * ch)))
+    return w, h, ch, raw
+
+
+LANCZOS_PRECISION_BITS = 32 - 8 - 2      # Pillow's fixed point: 8 bits of pixel, 2 of headroom for the negative lobes
+
+
+def _lanczos(x):
+    if not (-3.0 <= x < 3.0):
+        return 0.0
+    if x == 0.0:
+        return 1.0
+    a, b = x * math.pi, x / 3.0 * math.pi
+    return (math.sin(a) / a) * (math.sin(b) / b)
+
+
+def lanczos_taps(in_size, out_size):
+    """Pillow's resampling coefficients of `Image.resize(..., Image.LANCZOS)` for one axis, in its 22-bit fixed point:
+    (xmin (out,), count (out,), taps (out, ksize)) int32; output xx = clip8((2^21 + sum_j in[xmin + j] * taps[xx, j]) >> 22).
+    Formed in double, scalar by scalar with the C library's sin, as Pillow forms them: the last bit decides a rounding."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("sizes must be positive")
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 3.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    one = float(1 << LANCZOS_PRECISION_BITS)
+    xmin = np.zeros(out_size, np.int32)
+    count = np.zeros(out_size, np.int32)
+    taps = np.zeros((out_size, ksize), np.int32)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        lo = max(int(center - support + 0.5), 0)
+        hi = min(int(center + support + 0.5), in_size)
+        w = [_lanczos((x - center + 0.5) * ss) * ss for x in range(lo, hi)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        xmin[xx], count[xx] = lo, hi - lo
+        taps[xx, :hi - lo] = [int(v * one - 0.5) if v < 0 else int(v * one + 0.5) for v in w]
+    return xmin, count, taps
 
 
 def save_pfm(filename, image, scale=1):

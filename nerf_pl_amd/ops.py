@@ -1043,3 +1043,93 @@ def rgb_to_u8(rgb):
     if rgb.numel():
         check(_lib.load().nerfhip_mesh_rgb_to_u8(ptr(rgb), rgb.numel(), ptr(out), stream_ptr()), "nerfhip_mesh_rgb_to_u8")
     return out
+
+
+# ------------------------------------------------------------------------------- scene loading (datasets/blender.py:47-58, 90-95)
+def _require_u8(name, t):
+    if not torch.is_tensor(t):
+        raise NerfHipError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
+    if not t.is_cuda:
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: %s is a %s tensor (no CPU fallback)" % (name, t.device))
+    if t.dtype != torch.uint8:
+        raise NerfHipError("%s: expected uint8, got %s" % (name, t.dtype))
+    return _c(t)
+
+
+@device_guard
+def decode_png_batch(streams, H, W, ch, return_flags=False):
+    """nerfhip_png_unfilter: `streams` (n, H * (1 + W * ch)) uint8 on the device — the inflated IDAT data of n PNG files of one
+    size (imageio_min.png_inflate) — -> (n, H, W, ch) uint8 pixels.  A scanline with a filter type above 4 raises; with
+    return_flags the per-image int32 flags come back beside the pixels instead (no device-to-host read then)."""
+    streams = _require_u8("decode_png_batch streams", streams)
+    H, W, ch = int(H), int(W), int(ch)
+    if ch not in (1, 3, 4) or H < 1 or W < 1:
+        raise NerfHipError("decode_png_batch: H, W >= 1 and ch in (1, 3, 4), got %d x %d x %d" % (H, W, ch))
+    if streams.dim() != 2 or streams.shape[1] != H * (1 + W * ch):
+        raise NerfHipError("decode_png_batch: expected (n, %d) bytes per %d x %d x %d image, got %s"
+                           % (H * (1 + W * ch), H, W, ch, tuple(streams.shape)))
+    n = streams.shape[0]
+    out = torch.empty(n, H, W, ch, device=streams.device, dtype=torch.uint8)
+    flags = torch.empty(n, device=streams.device, dtype=torch.int32)
+    check(_lib.load().nerfhip_png_unfilter(ptr(streams), ptr(out), ptr(flags), n, H, W, ch, stream_ptr()), "nerfhip_png_unfilter")
+    if return_flags:
+        return out, flags
+    if n and bool(flags.any()):
+        raise NerfHipError("decode_png_batch: image(s) %s hold a scanline filter type above 4" % flags.nonzero().flatten().tolist())
+    return out
+
+
+_TAPS = {}
+
+
+def _lanczos_taps_device(in_size, out_size, device):
+    key = (int(in_size), int(out_size), str(device))
+    if key not in _TAPS:
+        from .imageio_min import lanczos_taps
+        if len(_TAPS) > 16:
+            _TAPS.clear()
+        _TAPS[key] = tuple(torch.from_numpy(a).to(device) for a in lanczos_taps(in_size, out_size))
+    return _TAPS[key]
+
+
+@device_guard
+def resize_rgba_lanczos(u8, w, h):
+    """nerfhip_resize_rgba_lanczos: `PIL.Image.resize((w, h), Image.LANCZOS)` of 8-bit RGBA images (n, H, W, 4) or (H, W, 4) on
+    the device, byte for byte (equal size: a copy)."""
+    u8 = _require_u8("resize_rgba_lanczos image", u8)
+    if u8.dim() not in (3, 4) or u8.shape[-1] != 4:
+        raise NerfHipError("resize_rgba_lanczos: expected (n, H, W, 4) or (H, W, 4), got %s" % (tuple(u8.shape),))
+    w, h = int(w), int(h)
+    single = u8.dim() == 3
+    n, H, W = (1,) + tuple(u8.shape[:2]) if single else tuple(u8.shape[:3])
+    if min(w, h, H, W) < 1:
+        raise NerfHipError("resize_rgba_lanczos: empty image")
+    dev = u8.device
+    out = torch.empty(n, h, w, 4, device=dev, dtype=torch.uint8)
+    th = _lanczos_taps_device(W, w, dev) if W != w else (None, None, None)
+    tv = _lanczos_taps_device(H, h, dev) if H != h else (None, None, None)
+    ws = torch.empty(n, H, w, 4, device=dev, dtype=torch.uint8) if (W != w and H != h) else None
+    check(_lib.load().nerfhip_resize_rgba_lanczos(ptr(u8), ptr(out), ptr(ws), n, H, W, h, w, ptr(th[0]), ptr(th[1]), ptr(th[2]),
+                                                  th[2].shape[1] if th[2] is not None else 0, ptr(tv[0]), ptr(tv[1]), ptr(tv[2]),
+                                                  tv[2].shape[1] if tv[2] is not None else 0, stream_ptr()),
+          "nerfhip_resize_rgba_lanczos")
+    return out[0] if single else out
+
+
+@device_guard
+def rgba_to_rgb_white(u8, out=None):
+    """nerfhip_rgba_to_rgb_white: (..., 4) uint8 RGBA -> (rgb (pixels, 3) float32 = ToTensor + the blend onto white of
+    blender.py:56-58, valid_mask (pixels,) bool = alpha > 0).  `out`: a contiguous (pixels, 3) float32 slice to write into."""
+    u8 = _require_u8("rgba_to_rgb_white image", u8)
+    if u8.dim() < 1 or u8.shape[-1] != 4:
+        raise NerfHipError("rgba_to_rgb_white: expected (..., 4) uint8, got %s" % (tuple(u8.shape),))
+    n = u8.numel() // 4
+    if out is None:
+        out = torch.empty(n, 3, device=u8.device, dtype=torch.float32)
+    else:
+        require_gpu(out)
+        if out.device != u8.device or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+            raise NerfHipError("rgba_to_rgb_white: out must be a contiguous (%d, 3) float32 tensor on %s" % (n, u8.device))
+    mask = torch.empty(n, device=u8.device, dtype=torch.uint8)
+    check(_lib.load().nerfhip_rgba_to_rgb_white(ptr(u8), ptr(out), ptr(mask), n, stream_ptr()), "nerfhip_rgba_to_rgb_white")
+    return out, mask.view(torch.bool)

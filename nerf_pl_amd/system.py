@@ -5,7 +5,7 @@ Same attribute names, `forward` chunk loop, `training_step` / `validation_step` 
 unchanged; it subclasses pytorch_lightning.LightningModule when that package exists and plain
 nn.Module otherwise (Lightning is not installed in this image; `fit()` below is a 30-line stand-in
 for Trainer.fit used by tests and bench — harness, not product).
-Datasets are injected (`train_dataset` / `val_dataset`): dataset I/O is out of scope.
+Datasets are injected (`train_dataset` / `val_dataset`); `nerf_pl_amd.datasets.BlenderDataset` loads a Blender scene on the GPU.
 """
 import os
 from collections import defaultdict
