@@ -31,6 +31,7 @@ extern "C" {
 #define NERFHIP_E_BADARG (-1)  /* null pointer / non-positive size / unsupported shape */
 #define NERFHIP_E_UNSUPPORTED (-2)
 #define NERFHIP_E_ALIGN (-3)   /* pointer not aligned as documented */
+#define NERFHIP_E_DATA (-4)    /* damaged input data (a JPEG scan that is truncated or holds an invalid code) */
 
 /* MLP arithmetic type (`dtype` arguments). */
 #define NERFHIP_F32 0  /* v_mfma_f32_32x32x2_f32, exact fp32 (parity configuration)      */
@@ -566,6 +567,35 @@ int nerfhip_resize_rgba_lanczos(const uint8_t* in, uint8_t* out, uint8_t* worksp
  * the product, the difference and the sum rounded separately; valid_mask (n) uint8 = alpha > 0 (NULL ok).  rgba (n,4) uint8,
  * 4-byte aligned; rgb may point into a larger (pixels,3) array, so a scene's colours are assembled in place.                  */
 int nerfhip_rgba_to_rgb_white(const uint8_t* rgba, float* rgb, uint8_t* valid_mask, int64_t n, nerfhip_stream_t stream);
+
+/* ---- JPEG decoding  (datasets/llff.py:226,312 `Image.open(p).convert('RGB')`; DESIGN.md "Scene loading") ---------------------
+ * Baseline sequential DCT, 8 bits, Huffman-coded, one interleaved scan; 1 component, or 3 (YCbCr) with luma sampling hs x vs =
+ * 1x1, 2x1 or 2x2 and chroma 1x1.  The results equal the bytes of Pillow's libjpeg-turbo with its defaults (islow inverse DCT,
+ * fancy upsampling).  The host parses the markers (nerf_pl_amd.imageio_min.jpeg_parse).
+ *
+ * jpeg_entropy_decode: HOST function — host pointers only, no GPU, launches nothing.  Huffman-decodes the entropy-coded segment
+ * `scan` (scan_bytes bytes, from behind the SOS header up to, not including, the marker that ends it; stuffed zeros and RSTm
+ * markers still inside) into coefficient blocks: coef[c] receives component c's blocks in raster order over
+ * (mcus_y * v_c) x (mcus_x * h_c) blocks, 64 int16 each in natural (row-major) order, DC prediction resolved, not dequantised.
+ * comp (n_comp,4) int32 = h, v, DC table id, AC table id per component.  huffman: 8 tables of 272 bytes (16 code-length counts +
+ * 256 symbols), table index = 4 * class + id; bit t of huffman_mask says table t is defined.  coef_blocks[c]: capacity of
+ * coef[c] in blocks.  restart_interval in MCUs, 0 = none.  Every read of `scan` and write of `coef` is bounds-checked:
+ * NERFHIP_E_DATA for a truncated or invalid stream, a table that is no prefix code or is missing, or a wrong restart marker;
+ * NERFHIP_E_BADARG for null / non-positive / too small arguments.                                                              */
+int nerfhip_jpeg_entropy_decode(const uint8_t* scan, int64_t scan_bytes, int n_comp, const int32_t* comp, const uint8_t* huffman,
+                                int huffman_mask, int mcus_x, int mcus_y, int restart_interval, int16_t* const* coef,
+                                const int64_t* coef_blocks);
+/* Bytes of the 8-bit component planes of one image (workspace of jpeg_decode); 0 for an unsupported size or sampling.          */
+size_t nerfhip_jpeg_planes_bytes(int H, int W, int n_comp, int hs, int vs);
+/* Device: n_images images of one size and sampling, two launches.  coef_* (n_images, blocks_c, 64) int16 as the entropy decoder
+ * leaves them (coef_cb / coef_cr NULL when n_comp == 1), quant (n_images, n_comp, 64) uint16 in natural order.  Launch 1:
+ * dequantise, libjpeg's integer "islow" inverse DCT (13-bit constants, 2 extra bits after the column pass), +128 and range limit
+ * -> planes (n_images * jpeg_planes_bytes).  Launch 2: libjpeg-turbo's triangle ("fancy") chroma upsampling for 2x1 and 2x2 —
+ * plain replication where the chroma plane is at most 2 samples wide —, its 16-bit fixed-point YCbCr -> RGB, crop -> out
+ * (n_images,H,W,4) uint8 with byte 3 = 255.  coef_* and quant 16-byte, planes 8-byte, out 4-byte aligned (NERFHIP_E_ALIGN).     */
+int nerfhip_jpeg_decode(const int16_t* coef_y, const int16_t* coef_cb, const int16_t* coef_cr, const uint16_t* quant,
+                        uint8_t* planes, uint8_t* out, int n_images, int H, int W, int n_comp, int hs, int vs,
+                        nerfhip_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -32,8 +32,8 @@ def default_mlp_dtype():
 
 def install(datasets=False):
     """Register this package's modules under the names the reference imports
-    (train.py:10-11, eval.py:9-10, models/rendering.py:2).  datasets=True: also `datasets` and `datasets.blender`
-    (train.py:8, eval.py:12) — off by default, so that inside a reference tree the reference's own loaders stay in charge."""
+    (train.py:10-11, eval.py:9-10, models/rendering.py:2).  datasets=True: also `datasets`, `datasets.blender` and
+    `datasets.llff` (train.py:8, eval.py:12) — off by default, so that inside a reference tree the reference's own loaders stay in charge."""
     from . import models, ops
     from .models import nerf, rendering
     sys.modules["models"] = models
@@ -46,3 +46,4 @@ def install(datasets=False):
         from . import datasets as ds
         sys.modules["datasets"] = ds
         sys.modules["datasets.blender"] = ds.blender
+        sys.modules["datasets.llff"] = ds.llff

@@ -129,6 +129,11 @@ SIGNATURES = {
     "nerfhip_resize_rgba_lanczos": [_c_void_p, _c_void_p, _c_void_p, _int, _int, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p,
                                     _int, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p],
     "nerfhip_rgba_to_rgb_white": [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p],
+    "nerfhip_jpeg_entropy_decode": [_c_void_p, _i64, _int, _c_void_p, _c_void_p, _int, _int, _int, _int, ctypes.POINTER(_c_void_p),
+                                    ctypes.POINTER(_i64)],
+    "nerfhip_jpeg_planes_bytes": [_int, _int, _int, _int, _int],
+    "nerfhip_jpeg_decode": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _int, _int, _int, _int, _int,
+                            _c_void_p],
 }
 
 
@@ -173,7 +178,8 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_mlp_dy_bytes": ctypes.c_size_t, "nerfhip_mlp_dw_workspace_bytes": ctypes.c_size_t,
              "nerfhip_mlp_dw_workspace_bytes_multi": ctypes.c_size_t,
              "nerfhip_linear_bwd_weight_workspace_bytes": ctypes.c_size_t,
-             "nerfhip_marching_cubes_workspace_bytes": ctypes.c_size_t, "nerfhip_mesh_cluster_workspace_bytes": ctypes.c_size_t}
+             "nerfhip_marching_cubes_workspace_bytes": ctypes.c_size_t, "nerfhip_mesh_cluster_workspace_bytes": ctypes.c_size_t,
+             "nerfhip_jpeg_planes_bytes": ctypes.c_size_t}
 
 _lib = None
 

@@ -1,7 +1,7 @@
 """Image / depth writers of the reference's eval loop (eval.py:119-149) without its imageio / cv2 dependencies:
 PNG (8-bit RGB or grey, zlib-deflated, filter 0), PFM (datasets/depth_utils.py:43-69 `save_pfm` / `read_pfm`, same bytes)
 and the raw little-endian float32 dump of `--depth_format bytes` (eval.py:135-137); and the host half of scene loading
-(nerf_pl_amd/datasets): the PNG container parser and Pillow's Lanczos taps.  Host-side, numpy only."""
+(nerf_pl_amd/datasets): the PNG container parser, the JPEG marker parser and Pillow's Lanczos taps.  Host-side, numpy only."""
 import math
 import re
 import struct
@@ -99,6 +99,162 @@ def png_inflate(data):
     if len(raw) != h * (1 + w * ch):
         raise ValueError("PNG data holds %d bytes, %d x %d x %d needs %d" % (len(raw), h, w, ch, h * (1 + w * ch)))
     return w, h, ch, raw
+
+
+# zigzag position -> natural (row-major) index of an 8 x 8 block
+JPEG_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+                        21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60,
+                        61, 54, 47, 55, 62, 63], np.int64)
+
+_SOF_NAMES = {0xc1: "extended sequential DCT", 0xc2: "progressive DCT", 0xc3: "lossless", 0xc5: "differential sequential DCT",
+              0xc6: "differential progressive DCT", 0xc7: "differential lossless", 0xc9: "arithmetic-coded sequential DCT",
+              0xca: "arithmetic-coded progressive DCT", 0xcb: "arithmetic-coded lossless", 0xcd: "arithmetic-coded differential",
+              0xce: "arithmetic-coded differential progressive", 0xcf: "arithmetic-coded differential lossless"}
+
+
+def jpeg_parse(data):
+    """JPEG file contents (bytes, or a path) -> dict: the counterpart of png_inflate.  Only what ops.jpeg_entropy_decode and
+    ops.decode_jpeg_batch take is accepted — baseline sequential DCT (SOF0), 8 bits, Huffman-coded, one interleaved scan; one
+    component, or three (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1 — anything else raises a ValueError that names
+    the problem and the file.  Keys:
+        width, height, restart_interval (MCUs, 0 = none), mcus_x, mcus_y
+        components       [(id, h, v, quantisation table id, DC table id, AC table id)] in scan order
+        quant            {id: (64,) uint16 in natural order}
+        huffman          {(class, id): (counts (16,) uint8, symbols (n,) uint8)}, class 0 = DC, 1 = AC
+        scan             the entropy-coded segment (bytes), stuffed zeros and RSTm markers still inside"""
+    name = "JPEG data"
+    if isinstance(data, str):
+        name = data
+        with open(data, "rb") as f:
+            data = f.read()
+    data = bytes(data)
+
+    def bad(what):
+        return ValueError("%s: %s" % (name, what))
+
+    if data[:2] != b"\xff\xd8":
+        raise bad("not a JPEG file")
+    pos, n = 2, len(data)
+    frame, quant, huffman, restart, adobe_transform = None, {}, {}, 0, None
+    while True:
+        while pos < n and data[pos] != 0xff:              # (garbage between segments is skipped, as libjpeg does)
+            pos += 1
+        while pos < n and data[pos] == 0xff:
+            pos += 1
+        if pos >= n:
+            raise bad("truncated: the file ends before a scan starts")
+        marker = data[pos]
+        pos += 1
+        if marker == 0xd8 or marker == 0x01 or 0xd0 <= marker <= 0xd7:
+            continue
+        if marker == 0xd9:
+            raise bad("no scan before the end-of-image marker")
+        if pos + 2 > n:
+            raise bad("truncated inside a marker segment")
+        length = struct.unpack(">H", data[pos:pos + 2])[0]
+        if length < 2 or pos + length > n:
+            raise bad("truncated inside a marker segment")
+        body = data[pos + 2:pos + length]
+        pos += length
+        if marker == 0xc0:
+            if frame is not None:
+                raise bad("more than one frame header")
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise bad("malformed frame header")
+            depth, height, width, ncomp = struct.unpack(">BHHB", body[:6])
+            if depth != 8:
+                raise bad("%d-bit samples are not supported (8 only)" % depth)
+            if height < 1 or width < 1:
+                raise bad("empty image (%d x %d)" % (width, height))
+            frame = (width, height, [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i])
+                                     for i in range(ncomp)])
+        elif marker in _SOF_NAMES:
+            depth = body[0] if body else 8
+            raise bad("%s%s (SOF%d) is not supported (baseline sequential DCT only)"
+                      % (_SOF_NAMES[marker], ", %d-bit" % depth if depth != 8 else "", marker - 0xc0))
+        elif marker == 0xcc:
+            raise bad("arithmetic coding is not supported")
+        elif marker == 0xdb:
+            at = 0
+            while at < len(body):
+                pq, tq = body[at] >> 4, body[at] & 15
+                size = 128 if pq else 64
+                if pq > 1 or tq > 3 or at + 1 + size > len(body):
+                    raise bad("malformed quantisation table")
+                if pq:
+                    raise bad("16-bit quantisation tables are not supported")
+                table = np.zeros(64, np.uint16)
+                table[JPEG_ZIGZAG] = np.frombuffer(body, np.uint8, 64, at + 1)
+                quant[tq] = table
+                at += 1 + size
+        elif marker == 0xc4:
+            at = 0
+            while at < len(body):
+                if at + 17 > len(body):
+                    raise bad("malformed Huffman table")
+                tc, th = body[at] >> 4, body[at] & 15
+                counts = np.frombuffer(body, np.uint8, 16, at + 1).copy()
+                total = int(counts.sum())
+                if tc > 1 or th > 3 or total > 256 or at + 17 + total > len(body):
+                    raise bad("malformed Huffman table")
+                huffman[(tc, th)] = (counts, np.frombuffer(body, np.uint8, total, at + 17).copy())
+                at += 17 + total
+        elif marker == 0xdd:
+            if len(body) != 2:
+                raise bad("malformed restart interval")
+            restart = struct.unpack(">H", body)[0]
+        elif marker == 0xee and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe_transform = body[11]
+        elif marker == 0xda:
+            break
+    if frame is None:
+        raise bad("scan without a frame header")
+    width, height, comps = frame
+    if len(comps) not in (1, 3):
+        raise bad("%d components are not supported (1, or 3 as YCbCr)" % len(comps))
+    if len(comps) == 3 and (adobe_transform == 0 or [c[0] for c in comps] == [82, 71, 66]):
+        raise bad("RGB-coded JPEG is not supported (YCbCr only)")
+    if len(body) < 1 or len(body) != 4 + 2 * body[0]:
+        raise bad("malformed scan header")
+    if body[0] != len(comps):
+        raise bad("a scan of %d of the %d components (non-interleaved file) is not supported" % (body[0], len(comps)))
+    ss, se, ahal = body[1 + 2 * body[0]:]
+    if (ss, se, ahal) != (0, 63, 0):
+        raise bad("spectral selection / successive approximation in a baseline scan")
+    components = []
+    for i, (cid, h, v, tq) in enumerate(comps):
+        sid, tables = body[1 + 2 * i], body[2 + 2 * i]
+        if sid != cid:
+            raise bad("scan components out of frame order")
+        td, ta = tables >> 4, tables & 15
+        if td > 3 or ta > 3:
+            raise bad("malformed scan header")
+        if tq not in quant:
+            raise bad("component %d names quantisation table %d, which the file does not define" % (cid, tq))
+        components.append((cid, h, v, tq, td, ta))
+    if len(components) == 1:
+        components[0] = (components[0][0], 1, 1) + components[0][3:]      # one component: its factors do not matter
+    else:
+        factors = [(c[1], c[2]) for c in components]
+        if factors[0] not in ((1, 1), (2, 1), (2, 2)) or factors[1:] != [(1, 1), (1, 1)]:
+            raise bad("sampling factors %s are not supported (luma 1x1, 2x1 or 2x2 with chroma 1x1)"
+                      % ", ".join("%dx%d" % f for f in factors))
+    # the entropy-coded segment ends at the first marker that is neither a stuffed zero nor RSTm
+    buf = np.frombuffer(data, np.uint8, offset=pos)
+    ff = np.flatnonzero(buf[:-1] == 0xff) if len(buf) > 1 else np.zeros(0, np.int64)
+    follow = buf[ff + 1]
+    stop = ff[(follow != 0) & ((follow < 0xd0) | (follow > 0xd7)) & (follow != 0xff)]
+    if len(stop) == 0:
+        raise bad("truncated: the entropy-coded data is not terminated by a marker")
+    end = int(stop[0])
+    if buf[end + 1] != 0xd9:
+        raise bad("more than one scan (marker 0x%02x follows the first) is not supported" % buf[end + 1])
+    if end == 0:
+        raise bad("empty scan")
+    hs, vs = components[0][1], components[0][2]
+    return {"width": width, "height": height, "components": components, "quant": quant, "huffman": huffman,
+            "restart_interval": restart, "mcus_x": -(-width // (8 * hs)), "mcus_y": -(-height // (8 * vs)),
+            "scan": data[pos:pos + end], "name": name}
 
 
 LANCZOS_PRECISION_BITS = 32 - 8 - 2      # Pillow's fixed point: 8 bits of pixel, 2 of headroom for the negative lobes

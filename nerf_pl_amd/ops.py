@@ -1133,3 +1133,73 @@ def rgba_to_rgb_white(u8, out=None):
     mask = torch.empty(n, device=u8.device, dtype=torch.uint8)
     check(_lib.load().nerfhip_rgba_to_rgb_white(ptr(u8), ptr(out), ptr(mask), n, stream_ptr()), "nerfhip_rgba_to_rgb_white")
     return out, mask.view(torch.bool)
+
+
+# --------------------------------------------------------------------------------------- JPEG decoding (datasets/llff.py:226, 312)
+def jpeg_entropy_decode(parsed):
+    """nerfhip_jpeg_entropy_decode (host, no GPU): the dict of imageio_min.jpeg_parse -> [per component: (blocks_y, blocks_x, 64)
+    int16 numpy coefficient blocks], natural order, DC prediction resolved, not dequantised, padded to whole MCUs."""
+    import numpy as np
+    comps = parsed["components"]
+    mx, my = int(parsed["mcus_x"]), int(parsed["mcus_y"])
+    table = np.zeros((8, 272), np.uint8)
+    mask = 0
+    for (tc, th), (counts, symbols) in parsed["huffman"].items():
+        table[4 * tc + th, :16] = counts
+        table[4 * tc + th, 16:16 + len(symbols)] = symbols
+        mask |= 1 << (4 * tc + th)
+    comp = np.ascontiguousarray([[c[1], c[2], c[4], c[5]] for c in comps], dtype=np.int32)
+    coef = [np.zeros((my * c[2], mx * c[1], 64), np.int16) for c in comps]
+    scan = np.frombuffer(parsed["scan"], np.uint8)
+    ptrs = (ctypes.c_void_p * len(comps))(*[a.ctypes.data for a in coef])
+    caps = (ctypes.c_int64 * len(comps))(*[a.shape[0] * a.shape[1] for a in coef])
+    code = _lib.load().nerfhip_jpeg_entropy_decode(scan.ctypes.data, len(scan), len(comps), comp.ctypes.data, table.ctypes.data, mask,
+                                                   mx, my, int(parsed["restart_interval"]), ptrs, caps)
+    if code != 0:
+        msg = _lib.load().nerfhip_error_string(code).decode()
+        raise NerfHipError("%s: nerfhip_jpeg_entropy_decode failed: %s (code %d)" % (parsed.get("name", "JPEG data"), msg, code))
+    return coef
+
+
+def _require_i16(name, t, device, shape):
+    if not torch.is_tensor(t):
+        raise NerfHipError("%s: expected a torch tensor, got %s" % (name, type(t).__name__))
+    if not t.is_cuda:
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: %s is a %s tensor (no CPU fallback)" % (name, t.device))
+    if t.dtype != torch.int16 or tuple(t.shape) != tuple(shape) or (device is not None and t.device != device):
+        raise NerfHipError("%s: expected int16 %s on %s, got %s %s on %s" % (name, tuple(shape), device, t.dtype, tuple(t.shape), t.device))
+    return _c(t)
+
+
+@device_guard
+def decode_jpeg_batch(coefs, quant, H, W, hs=1, vs=1):
+    """nerfhip_jpeg_decode: n JPEG images of one size and sampling -> (n, H, W, 4) uint8 RGBX (X = 255) on the device, the bytes
+    of PIL's `Image.open(p).convert('RGB')`.  coefs: per component (1, or 3 = Y Cb Cr) an int16 tensor (n, blocks_c, 64) — or
+    (n, blocks_y, blocks_x, 64) — as jpeg_entropy_decode leaves them; quant (n, n_comp, 64) int16: each image's quantisation
+    tables in natural order, per component; hs, vs: the luma sampling factors (chroma is 1 x 1)."""
+    if torch.is_tensor(coefs):
+        coefs = [coefs]
+    coefs = list(coefs)
+    H, W, hs, vs = int(H), int(W), int(hs), int(vs)
+    n_comp = len(coefs)
+    lib = _lib.load()
+    plane_bytes = lib.nerfhip_jpeg_planes_bytes(H, W, n_comp, hs, vs) if n_comp in (1, 3) else 0
+    if plane_bytes == 0:
+        raise NerfHipError("decode_jpeg_batch: %d component(s) of %d x %d with luma sampling %dx%d is not supported (1 component, "
+                           "or 3 with 1x1, 2x1 or 2x2)" % (n_comp, W, H, hs, vs))
+    if not torch.is_tensor(coefs[0]) or coefs[0].dim() < 2:
+        raise NerfHipError("decode_jpeg_batch: coefs must be (n, blocks, 64) int16 tensors")
+    n, dev = coefs[0].shape[0], coefs[0].device
+    mx, my = -(-W // (8 * hs)), -(-H // (8 * vs))
+    flat = []
+    for c, t in enumerate(coefs):
+        blocks = mx * my * (hs * vs if c == 0 else 1)
+        if torch.is_tensor(t) and t.dim() == 4:
+            t = t.reshape(t.shape[0], -1, 64)
+        flat.append(_require_i16("decode_jpeg_batch coefs[%d]" % c, t, dev, (n, blocks, 64)))
+    quant = _require_i16("decode_jpeg_batch quant", quant, dev, (n, n_comp, 64))
+    out = torch.empty(n, H, W, 4, device=dev, dtype=torch.uint8)
+    planes = torch.empty(n * plane_bytes, device=dev, dtype=torch.uint8)
+    check(lib.nerfhip_jpeg_decode(ptr(flat[0]), ptr(flat[1]) if n_comp == 3 else None, ptr(flat[2]) if n_comp == 3 else None,
+                                  ptr(quant), ptr(planes), ptr(out), n, H, W, n_comp, hs, vs, stream_ptr()), "nerfhip_jpeg_decode")
+    return out
