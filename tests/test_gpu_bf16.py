@@ -5,7 +5,11 @@ at n >= 1000 points.
 
 The scene is procedural (tests/helpers.analytic_scene: closed-form colours of a soft ball, independent of both the HIP
 path and the oracle) and easy enough to pass 25 dB within a few hundred steps, where PSNR is still sensitive.
-Every configuration starts from the same default-init weights and consumes the same ray batches and RNG draws."""
+Every configuration starts from the same default-init weights and consumes the same ray batches and RNG draws.
+
+These gates compare with the fp32 oracle and therefore allow the bf16 rounding itself (10 % of a gradient tensor).  Exactness of
+the bf16 kernels — every layer, chain layer and weight-gradient job against a model that rounds where they round — is
+tests/test_gpu_bf16_exact.py (model and decoder: oracle/bf16_exact.py, tests/test_bf16_exact_host.py)."""
 from argparse import Namespace
 
 import pytest

@@ -23,6 +23,9 @@ def _oracle_param_grads(p, x, g_out):
 @pytest.mark.parametrize("dtype,tol", [("fp32", 2e-4), ("bf16", 4e-2), ("bf16_f8", 4e-2)])
 @pytest.mark.parametrize("n", [1, 33, 300, 1000])
 def test_mlp_backward_embedded_vs_autograd(dev, dtype, tol, n):
+    """Forward and the 24 gradients of the fused MLP against autograd through the fp32 oracle.  For the reduced-precision modes this
+    is a direction gate that has to allow the bf16 rounding; what the bf16 kernels compute EXACTLY, stage by stage on the same inputs,
+    is pinned by tests/test_gpu_bf16_exact.py."""
     g = torch.Generator().manual_seed(n)
     p = O.make_params(21, 3.0, 0.1)
     pts = torch.rand(n, 3, generator=g) * 4 - 2
