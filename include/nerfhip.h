@@ -222,6 +222,8 @@ int nerfhip_mlp_pack_weights_train_multi(const float* const* weights_host, const
                                          nerfhip_stream_t stream);
 size_t nerfhip_mlp_dy_bytes(int64_t n_points, int dtype);
 int nerfhip_mlp_dw_splits(int64_t n_points, int dtype);   /* total (job, point-split) workgroups = partial slabs */
+/* The workspace size queries and the launches compute the SAME split plan, a function of (points per model, dtype) alone: what a
+ * query returns is exactly what the launch with those arguments writes, with or without regenerated encodings.               */
 size_t nerfhip_mlp_dw_workspace_bytes(int64_t n_points, int dtype);
 int nerfhip_mlp_bwd(const float* g_out, const float* out, int64_t n, const void* packed_bwd, const void* acts,
                     void* dys, void* dw_workspace, float* const* grad_w_host, float* const* grad_b_host,

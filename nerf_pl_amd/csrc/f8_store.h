@@ -3,10 +3,6 @@
 #pragma once
 #include "mlp_device.h"
 
-#ifndef NERFHIP_F8EXP
-#define NERFHIP_F8EXP 0         // timing experiments only (results invalid): 1 = convert but do not store, 2 = store without converting
-#endif
-
 namespace nerfhip {
 
 // ---- training, fp8 storage (NERFHIP_BF16_F8, mlp_layout.h "fp8 storage of the saved tensors") -------------------------
@@ -56,13 +52,9 @@ __device__ __forceinline__ void save_pair_f8(int& pending, uint8_t* tile_ptr, in
     pk[0] = d0; pk[1] = d1;
     slab_to_f8(s1, scale, d0, d1);
     pk[2] = d0; pk[3] = d1;
-#if NERFHIP_F8EXP == 1
-    asm volatile("" ::"v"(pk));
-#else
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(tile_ptr + (size_t)pair * kPieceBytes, 0, kPieceBytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (unsigned)lane * 16u, 0, NERFHIP_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (unsigned)lane * 16u, 0, kStoreAux);
     pending += 1;
-#endif
 }
 // one scale dword (activations: one per (wave tile, section)), written by lane 0
 __device__ __forceinline__ void save_scale_f8(int& pending, uint8_t* tile_ptr, int scale_off, int index, int sb, int lane) {
@@ -72,6 +64,7 @@ __device__ __forceinline__ void save_scale_f8(int& pending, uint8_t* tile_ptr, i
 }
 // ---- e5m2 ("bf8") variant for dY: 5 exponent bits keep the heavy tail of the per-point gradient magnitudes (samples off the
 // surface carry dY 1e-3 .. 1e-6 of the tile's maximum; e4m3's 14 binades of normals under ONE scale per tile flush them)
+constexpr int kDyMfmaFormat = 1;      // dY as an operand of v_mfma_scale_f32_32x32x64_f8f6f4: format code 1 = e5m2 (0 = e4m3)
 __device__ __forceinline__ int bf8_scale_byte(unsigned maxbits) {     // |x| / 2^(E-127) < 2^15 <= 57344 (e5m2 max)
     const int e = (int)((maxbits >> 23) & 0xffu) - 14;
     return e < 1 ? 1 : e;
@@ -99,13 +92,10 @@ __device__ __forceinline__ void save_pair_bf8(int& pending, uint8_t* tile_ptr, i
     slab_to_bf8(s1, scale, d0, d1);
     pk[2] = d0; pk[3] = d1;
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(tile_ptr + (size_t)pair * kPieceBytes, 0, kPieceBytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (unsigned)lane * 16u, 0, NERFHIP_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (unsigned)lane * 16u, 0, kStoreAux);
     pending += 1;
 }
 __device__ __forceinline__ int bf8_block_scale(float lane_max) { return bf8_scale_byte(wave_max_u32(__float_as_uint(lane_max))); }
-#ifndef NERFHIP_F8_DY_E5M2
-#define NERFHIP_F8_DY_E5M2 1
-#endif
 // scale byte of a block from the lanes' partial maxima (one DPP reduction)
 __device__ __forceinline__ int f8_block_scale(float lane_max) { return f8_scale_byte(wave_max_u32(__float_as_uint(lane_max))); }
 

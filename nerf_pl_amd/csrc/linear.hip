@@ -15,8 +15,6 @@
 // with g = gy * act'(y) formed while the operand is loaded (ReLU: y > 0; Sigmoid: y (1 - y), torch's sigmoid_backward).
 // Precision: NERFHIP_F32 = v_mfma_f32_32x32x2_f32 (every product and sum in fp32); NERFHIP_BF16 / _BF16_F8 = operands rounded to
 // bf16 (RNE) on their way into LDS, v_mfma_f32_32x32x16_bf16, fp32 accumulation.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "mlp_device.h"
@@ -26,10 +24,7 @@ namespace lin {
 
 constexpr int kTileI = 128;  // output tile: 128 rows (i) x 128 or 256 columns (j); every wave a 64 x 64 sub-tile (2 x 2 MFMA blocks)
 constexpr int kStage = 32;   // reduction steps per LDS stage
-#ifndef NERFHIP_LIN_DEPTH
-#define NERFHIP_LIN_DEPTH 1  // 2 (a second register buffer) costs the second wave per SIMD: 192-248 VGPRs + 64 accumulators
-#endif
-constexpr int kDepth = NERFHIP_LIN_DEPTH;
+constexpr int kDepth = 1;    // 2 (a second register buffer) costs the second wave per SIMD: 192-248 VGPRs + 64 accumulators
 
 // One GEMM operand: a (rows x K) matrix of which the kernel needs tiles of 128 rows x 32 reduction steps.
 //   ROWC = false ("k-contiguous"):   element (r, k) = p[r * s + k]      activations x / g as the point-major side
@@ -325,11 +320,7 @@ __global__ __launch_bounds__(256) void linear_dw_reduce_kernel(const float* __re
     *dst = accumulate ? nh_add(*dst, s) : s;
 }
 
-static int tile_j(int64_t J) {      // the 8-wave 128 x 256 tile when there is more than one 128-column tile
-    static const char* force = getenv("NERFHIP_LIN_TJ");                        // A/B: NERFHIP_LIN_TJ=128
-    if (force && force[0] == '1') return 128;
-    return J > 128 ? 256 : 128;
-}
+static int tile_j(int64_t J) { return J > 128 ? 256 : 128; }      // the 8-wave 128 x 256 tile when there is more than one 128-column tile
 static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 struct DwPlan {

@@ -84,10 +84,10 @@ extern "C" int nerfhip_mlp_bwd_multi_rays(int n_models, const float* const* g_ou
                                           const nerfhip_adam_fused* adam, const nerfhip_enc_source* enc, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(n_models >= 1 && n_models <= nerfhip::kDwMaxModels);
     if (!valid_dtype(dtype)) return NERFHIP_E_UNSUPPORTED;
-    bool regen[nerfhip::kDwMaxModels] = {false, false};
+    bool regen[nerfhip::kDwMaxModels] = {false, false};      // (kernel arguments only: the plan below is the size query's)
     if (enc) {
-        // the encodings are formed in the bf16 weight-gradient kernel's dir + sigma job class only
-        if (dtype != NERFHIP_BF16 || !NERFHIP_DW_FOLD_SIGMA || !NERFHIP_DW_BLOCKED) return NERFHIP_E_UNSUPPORTED;
+        // the encodings are formed in the bf16 weight-gradient kernel only
+        if (dtype != NERFHIP_BF16) return NERFHIP_E_UNSUPPORTED;
         for (int m = 0; m < n_models; ++m) {
             if (!enc->rays[m]) continue;                              // (this model's encodings were saved)
             NERFHIP_CHECK_ARG(enc->z[m] && enc->S[m] > 0 && enc->S[m] % 32 == 0 && n_host[m] % 256 == 0 && n_host[m] % enc->S[m] == 0);
@@ -107,7 +107,7 @@ extern "C" int nerfhip_mlp_bwd_multi_rays(int n_models, const float* const* g_ou
              ((uintptr_t)dys_host[m])) & 15)
             return NERFHIP_E_ALIGN;
     }
-    const int nwg = dw_plan(n_host, n_models, dtype, &jt, regen);
+    const int nwg = dw_plan(n_host, n_models, dtype, &jt);
     for (int m = 0; m < nerfhip::kDwMaxModels; ++m) {
         const bool on = m < n_models && regen[m];
         jt.enc_rays[m] = on ? enc->rays[m] : nullptr;

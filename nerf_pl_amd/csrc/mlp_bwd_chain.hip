@@ -9,10 +9,6 @@
 #include "f8_store.h"
 #include "mlp_bwd_chain.h"
 
-#ifndef NERFHIP_CHAIN_PK_GATE
-#define NERFHIP_CHAIN_PK_GATE 1   // bf16 chain: ReLU gates applied to the PACKED bf16 pairs (3 packed ops per pair instead of 2 per value)
-#endif
-
 namespace nerfhip {
 
 __device__ __forceinline__ float slab_absmax8(const bf16x8& s) {
@@ -31,15 +27,10 @@ __device__ __forceinline__ float slab_absmax8(const f32x8& s) { return 0.0f; }  
 // 226.9 -> 217.5 us with depth 2 (depth 1: 216-218, depth 3: 219); the e5m2-storing variant sits at its 256-register budget,
 // where the ring costs 16-48 spilled registers: 209.3 (none) / 212 (1) / 212 (2) / 222 us (3) — the two waves of a SIMD already
 // cover each other's LDS round trips there.
-#ifndef NERFHIP_CHAIN_BURST
-#define NERFHIP_CHAIN_BURST 2
-#endif
-#ifndef NERFHIP_CHAIN_DEPTH
-#define NERFHIP_CHAIN_DEPTH 2
-#endif
-#ifndef NERFHIP_CHAIN_DEPTH_F8
-#define NERFHIP_CHAIN_DEPTH_F8 0
-#endif
+constexpr int kChainDepthBf16 = 2, kChainDepthF8 = 0;      // the bf16-storing | the e5m2-storing variant
+// slabs per run of back-to-back dY stores (2 = each tile's pair as soon as it is gated; the slabs of a layer stay in registers as the
+// next layer's operands anyway, so holding a run back costs no register)
+constexpr int kChainBurst = 2;
 // the W^T stream's ring (mlp_device.h): the chain stores dY all along, so its boundaries always count stores
 template <int PREC> using BwdStream = RingStream<PrecTraits<PREC>::NW, bwd_chunks(PREC), true>;
 
@@ -60,22 +51,12 @@ __device__ __forceinline__ void store_slab(int& pending, __amdgpu_buffer_rsrc_t 
     store_slab_b128(pending, rsrc, s, voff + soff);      // (the section offset in VOFFSET, soffset 0: mlp_device.h)
 }
 
-// dY pair store / block scale in the configured 8-bit format (f8_store.h: e5m2 by default, see NERFHIP_F8_DY_E5M2)
+// dY pair store / block scale in dY's 8-bit format: e5m2 (f8_store.h)
 __device__ __forceinline__ void save_dy_pair(int& pending, uint8_t* dy_tile, int pair, const bf16x8& s0, const bf16x8& s1, int sb, int lane) {
-#if NERFHIP_F8_DY_E5M2
     save_pair_bf8(pending, dy_tile, pair, s0, s1, sb, lane);
-#else
-    save_pair_f8(pending, dy_tile, pair, s0, s1, sb, lane);
-#endif
 }
 __device__ __forceinline__ void save_dy_pair(int&, uint8_t*, int, const f32x8&, const f32x8&, int, int) {}    // (never used: fp8 storage is bf16-only)
-__device__ __forceinline__ int dy_block_scale(float lane_max) {
-#if NERFHIP_F8_DY_E5M2
-    return bf8_block_scale(lane_max);
-#else
-    return f8_block_scale(lane_max);
-#endif
-}
+__device__ __forceinline__ int dy_block_scale(float lane_max) { return bf8_block_scale(lane_max); }
 
 // sign-extended one-bit field of a gate word: 0 or ~0.  (As inline asm: written with the builtin or plain C, hipcc turns the
 // constant-position extract + AND into v_and + v_cmp + v_cndmask, three VALU per value instead of two.)
@@ -130,7 +111,7 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
     // fragment into the same four registers right before its MFMA: 480 of the kernel's 716 MFMAs sit behind an
     // `s_waitcnt lgkmcnt(0)` of their own.)
     constexpr int NFR = NT * NKS;
-    constexpr int kChainDepth = F8 ? NERFHIP_CHAIN_DEPTH_F8 : NERFHIP_CHAIN_DEPTH;
+    constexpr int kChainDepth = F8 ? kChainDepthF8 : kChainDepthBf16;
     [[maybe_unused]] bf16x8 afr[kChainDepth > 0 ? kChainDepth : 1];
     [[maybe_unused]] auto frag_read = [&](auto ic) -> bf16x8 {
         constexpr int g = G0 + decltype(ic)::value * PPF;
@@ -182,7 +163,6 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
             }
         }
         // ---- epilogue of tile t: g wrt pre-activation = g * relu'(pre-act) (gate bit: mlp_layout.h gate_word / gate_bit) ----
-#if NERFHIP_CHAIN_PK_GATE
         if constexpr (PREC == NERFHIP_BF16 && MASK) {
             // the gates on PACKED pairs: dword k of a gate word holds the pair's two bits at bit 15 - k of its half-words, so
             // (half << k) >> 15 (arithmetic) is 0xffff / 0 per half: shift, shift, and = 3 packed operations per pair (2 per
@@ -207,9 +187,7 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
                 out[2 * t + (p >> 2)][2 * (p & 3)] = gated[0];
                 out[2 * t + (p >> 2)][2 * (p & 3) + 1] = gated[1];
             });
-        } else
-#endif
-        {
+        } else {
         float v[16];
         static_for<0, 16>([&](auto rc) {
             constexpr int r = decltype(rc)::value;           // slab 2t + (r >> 3), slot r & 7
@@ -232,9 +210,7 @@ __device__ __forceinline__ int run_bwd_layer_tm(BwdStream<PREC>& st, const unsig
             // per-tile offsets are immediates (soffset stays 0: gfx950 store-data hazard, mlp_device.h store_slab_b128)
             __amdgpu_buffer_rsrc_t dys_l = __builtin_amdgcn_make_buffer_rsrc(dy_tile + (size_t)dy_sec * 64 * sizeof(Slab) * act_il(PREC), 0,
                                                                               (int)(2 * NT * 64 * sizeof(Slab) * act_il(PREC)), 0x00020000);
-            // NERFHIP_CHAIN_BURST slabs per run of back-to-back stores (2 = each tile's pair as soon as it is gated; the slabs of a
-            // layer stay in registers as the next layer's operands anyway, so holding a run back costs no register)
-            constexpr int TB = NERFHIP_CHAIN_BURST / 2 > 0 ? NERFHIP_CHAIN_BURST / 2 : 1;
+            constexpr int TB = kChainBurst / 2 > 0 ? kChainBurst / 2 : 1;      // tiles per run of back-to-back stores
             if constexpr ((t + 1) % TB == 0 || t == NT - 1) {
                 constexpr int t0 = (t / TB) * TB;
 #pragma unroll
@@ -292,20 +268,12 @@ void mlp_bwd_chain_kernel(BwdChainArgs A, const float* __restrict__ g_scale) {
     constexpr int IL = act_il(PREC, F8);     // the saved blocks' pieces are IL KiB apart (mlp_layout.h: bf16 slabs 8, otherwise 1)
     __amdgpu_buffer_rsrc_t acts = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint8_t*>(acts_base) + tile_block_off(tile, kActTile, IL), 0, kActTile * IL, 0x00020000);
-#ifdef NERFHIP_EXP_TILEWRAP    // timing experiment only (results invalid): every wave stores into one of a few L2-resident tile blocks
-    uint8_t* dy_tile = dys_base + tile_block_off(tile & (NERFHIP_EXP_TILEWRAP - 1), kDyTile, IL);
-#else
     uint8_t* dy_tile = dys_base + tile_block_off(tile, kDyTile, IL);
-#endif
     __amdgpu_buffer_rsrc_t dys = __builtin_amdgcn_make_buffer_rsrc(dy_tile, 0, kDyTile * IL, 0x00020000);
 
 
     BwdStream<PREC> st;
-#if NERFHIP_DMA_SADDR
     st.gsrc = packed_bwd;
-#else
-    st.gsrc = packed_bwd + lane * 16;
-#endif
     st.voff = (unsigned)lane * 16u;
     st.lds_base = (unsigned)(uintptr_t)ring;
     st.wave = wave;
@@ -337,15 +305,9 @@ void mlp_bwd_chain_kernel(BwdChainArgs A, const float* __restrict__ g_scale) {
     }
     if constexpr (F8) {
         if constexpr (PREC == NERFHIP_BF16) {
-#if NERFHIP_F8_DY_E5M2
             const int sb_rgb = bf8_block_scale(slab_absmax8(g_rgb)), sb_sig = bf8_block_scale(slab_absmax8(g_sig));
             save_pair_bf8(st.pending, dy_tile, kDyRgb / 2, g_rgb, zero_slab, sb_rgb, lane);
             save_pair_bf8(st.pending, dy_tile, kDySigma / 2, g_sig, zero_slab, sb_sig, lane);
-#else
-            const int sb_rgb = f8_block_scale(slab_absmax8(g_rgb)), sb_sig = f8_block_scale(slab_absmax8(g_sig));
-            save_pair_f8(st.pending, dy_tile, kDyRgb / 2, g_rgb, zero_slab, sb_rgb, lane);
-            save_pair_f8(st.pending, dy_tile, kDySigma / 2, g_sig, zero_slab, sb_sig, lane);
-#endif
             save_scale_f8(st.pending, dy_tile, f8_dy_scale_off(), f8_dy_section(kDyRgb), sb_rgb, lane);
             save_scale_f8(st.pending, dy_tile, f8_dy_scale_off(), f8_dy_section(kDySigma), sb_sig, lane);
         }

@@ -7,9 +7,6 @@
 
 typedef struct ihipStream_t* hipStream_t;      // (as <hip/hip_runtime_api.h> declares it)
 
-#ifndef NERFHIP_DW_BLOCKED
-#define NERFHIP_DW_BLOCKED 1     // a split's tiles are one contiguous range (0: strided), see mlp_bwd_dw_kernel
-#endif
 #ifndef NERFHIP_DW_PROBE
 #define NERFHIP_DW_PROBE 0       // debug builds: every wave of the dW kernels accumulates where its cycles go (tools/dw_probe.py)
 #endif

@@ -13,37 +13,16 @@ namespace nerfhip {
 __device__ unsigned g_dw_probe[1024 * 8 * 8];       // [workgroup][wave][iters, wait, barrier, issue, compute, total, job, depth]
 #endif
 
-#ifndef NERFHIP_DW_RING_KB
-#define NERFHIP_DW_RING_KB 160   // bf16 dW ring: the whole LDS of a CU, cut into as many stages as the JOB's stage size allows (round 4; the
-                                 // depth itself measured neutral — 4 stages of 36 KiB run the same 480 us — the waves never wait for data)
-#endif
-#ifndef NERFHIP_DW_MAXDEPTH
-#define NERFHIP_DW_MAXDEPTH 12
-#endif
-#ifndef NERFHIP_DW_SHARE_LAST
-#define NERFHIP_DW_SHARE_LAST 1  // bf16: the waves share a stage's last REM < 8 pieces under EXEC masks (0 = the surplus waves re-fetch the last piece)
-#endif
-#ifndef NERFHIP_DW_RD
-#define NERFHIP_DW_RD 5          // bf16: B fragments in flight (ring of RD, RD - 1 steps ahead of the MFMA)
-#endif
-#ifndef NERFHIP_DW_SPREAD
-#define NERFHIP_DW_SPREAD 1      // bf16: the next stage's DMAs issued between the current stage's MFMAs (0 = in one block after the barrier)
-#endif
-
-#ifndef NERFHIP_DW_SPLIT2D
-#define NERFHIP_DW_SPLIT2D 1     // bf16, jobs with 8 dY tiles and 8 / 10 X tiles: wave = 2 dY tiles x (4 | 5) X tiles instead of 1 x (8 | 10) — 6 | 7
-#endif                           // operand fragments from LDS per k-step instead of 9 | 11 (round 6: profiles/r06_dw_bisect.txt, variant M)
-#ifndef NERFHIP_DW_RD2
-#define NERFHIP_DW_RD2 4         // ... its B fragments in flight
-#endif
-#ifndef NERFHIP_DW_BIAS_DOT2
-#define NERFHIP_DW_BIAS_DOT2 1   // bf16 bias partials by v_dot2_f32_bf16 against (1, 1), two chains, instead of 8 dependent cvt + add per fragment
-#endif
+// bf16 dW ring: the whole LDS of a CU, cut into as many stages as the JOB's stage size allows, at most kDwMaxDepth (round 4; the depth
+// itself measured neutral — 4 stages of 36 KiB run the same 480 us — the waves never wait for data)
+constexpr int kDwRingKiB = 160, kDwMaxDepth = 12;
+// bf16: B fragments in flight (ring of RD, RD - 1 steps ahead of the MFMA): one dY tile per wave | the 2-D wave split (SPLIT2D below)
+constexpr int kDwFragRing = 5, kDwFragRing2D = 4;
 
 template <int PREC> struct DwTraits;
 template <> struct DwTraits<NERFHIP_BF16> {
     static constexpr int SPP = 1;            // 1 KiB pieces per slab
-    static constexpr int RING_BYTES = NERFHIP_DW_RING_KB * 1024;      // cut into stages of the job class's own size (dw_depth)
+    static constexpr int RING_BYTES = kDwRingKiB * 1024;      // cut into stages of the job class's own size (dw_depth)
     static constexpr int DEPTH = 0, STAGE_BYTES = 0;                  // (fp32 only: a fixed 2 x 72 KiB ring)
 };
 template <> struct DwTraits<NERFHIP_F32> {
@@ -58,25 +37,21 @@ template <> struct DwTraits<NERFHIP_F32> {
 template <int PREC> NH_HD constexpr int dw_depth(int pieces) {
     if (PREC != NERFHIP_BF16) return DwTraits<PREC>::DEPTH;
     const int d = DwTraits<PREC>::RING_BYTES / (pieces * kPieceBytes);
-    return d > NERFHIP_DW_MAXDEPTH ? NERFHIP_DW_MAXDEPTH : d;
+    return d > kDwMaxDepth ? kDwMaxDepth : d;
 }
 
-// sum of a bf16 A fragment's 8 values into two running fp32 partials (the bias gradient: dY summed over the points)
+// sum of a bf16 A fragment's 8 values into two running fp32 partials (the bias gradient: dY summed over the points): v_dot2_f32_bf16
+// against (1, 1), two chains, instead of 8 dependent cvt + add per fragment
 __device__ __forceinline__ void dw_bias_sum(const bf16x8& a, float& s0, float& s1) {
-#if NERFHIP_DW_BIAS_DOT2
     const bf16x2 one = {(__bf16)1.0f, (__bf16)1.0f};
     s0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a[0], a[1]}, one, s0, false);
     s1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a[2], a[3]}, one, s1, false);
     s0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a[4], a[5]}, one, s0, false);
     s1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2{a[6], a[7]}, one, s1, false);
-#else
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s0 += (float)a[j];
-#endif
 }
 
 // Slab `ks` (wave-uniform) of the F-frequency encoding of v in the forward's slot order — the arithmetic of the bf16 forward's
-// encode_slots (mlp_fwd_kernel.h, NERFHIP_FAST_SINCOS path: x / 2 pi as a hi + lo pair, exact power-of-two scaling, v_fract, hardware
+// encode_slots (mlp_fwd_kernel.h, the hardware-sincos path: x / 2 pi as a hi + lo pair, exact power-of-two scaling, v_fract, hardware
 // v_sin / v_cos in revolutions), operation for operation, so that the regenerated operand has the bits the forward multiplied by:
 // pair p = 4 ks + q is channel p % 3 at frequency 2^(2 (p / 3) + h); the slots behind the last pair hold the identity channels.
 template <int F, int SLABS>
@@ -142,16 +117,11 @@ void mlp_bwd_dw_kernel(DwJobTable jobs, float* __restrict__ slabs) {
     const int n_ot = jb.dy_slabs / 2;
     const int n_xs = jb.x1_slabs + jb.x2_slabs;
     const int n_xt = n_xs / 2;
-#if NERFHIP_DW_BLOCKED
     // contiguous tile range per split (consecutive iterations stay inside the same 2 MiB pages: a tile block is
     // 167 KiB; the strided assignment touched 2-3 new pages per iteration per workgroup)
     const int64_t per = (ntiles + nsplit - 1) / nsplit;
     const int64_t t_first = (int64_t)split * per;
     const int64_t my_tiles = (t_first >= ntiles) ? 0 : ((ntiles - t_first < per) ? ntiles - t_first : per);
-#else
-    const int64_t t_first = split;
-    const int64_t my_tiles = (ntiles - split + nsplit - 1) / nsplit;   // tiles split, split+nsplit, ...
-#endif
     const unsigned lds_base = (unsigned)(uintptr_t)ring;
 
     // stage image: [dy slabs][x1 slabs][x2 slabs], each slab SPP 1 KiB pieces at 1 KiB pitch.  The DMA writes
@@ -206,7 +176,9 @@ void mlp_bwd_dw_kernel(DwJobTable jobs, float* __restrict__ slabs) {
         constexpr bool FOLD = NXT == 9 && NSL == kDwFoldStageSlabs;
         // round 6, bf16: the classes with 8 dY tiles and 8 | 10 X tiles — (8, 32), (10, 36): 85 % of the launch's
         // workgroups — give wave (wi = wave >> 1, wj = wave & 1) the dY tiles 2 wi, 2 wi + 1 against the X tiles XW wj .. XW wj + XW - 1
-        constexpr bool SPLIT2D = (PREC == NERFHIP_BF16) && NERFHIP_DW_SPLIT2D && (NXT == 8 || NXT == 10) && (NSL - 2 * NXT >= 16);
+        // (XW = 4 | 5) instead of 1 x (8 | 10): 6 | 7 operand fragments from LDS per k-step instead of 9 | 11
+        // (profiles/r06_dw_bisect.txt, variant M)
+        constexpr bool SPLIT2D = (PREC == NERFHIP_BF16) && (NXT == 8 || NXT == 10) && (NSL - 2 * NXT >= 16);
         constexpr int NP = NSL * SPP;                              // 1 KiB pieces per stage
         constexpr int NPD = NP - ENC;                              // ... of which are fetched
         constexpr int LPWD = (NPD + 7) / 8;                        // piece DMAs per wave per stage
@@ -226,7 +198,7 @@ void mlp_bwd_dw_kernel(DwJobTable jobs, float* __restrict__ slabs) {
         const uint8_t* dbase = nullptr;
         unsigned slot = 0;
         auto stage_tile = [&](int64_t it) {
-            int64_t T = t_first + (it < my_tiles ? it : my_tiles - 1) * (NERFHIP_DW_BLOCKED ? 1 : nsplit);   // past the end: re-fetch
+            int64_t T = t_first + (it < my_tiles ? it : my_tiles - 1);   // past the end: re-fetch
             if (T >= ntiles) T = ntiles - 1;
             return T;
         };
@@ -289,7 +261,7 @@ void mlp_bwd_dw_kernel(DwJobTable jobs, float* __restrict__ slabs) {
         // 8 - REM waves re-fetching the stage's last piece: every wave still issues the same count (one immediate vmcnt), and no byte
         // is fetched twice (round 4: the re-fetches were up to a quarter of a small job's DMAs, and nt loads do not stay in L2).
         constexpr int REM = NPD % 8;
-        constexpr bool SHARE_LAST = (PREC == NERFHIP_BF16) && NERFHIP_DW_SHARE_LAST && (REM == 4 || REM == 2);
+        constexpr bool SHARE_LAST = (PREC == NERFHIP_BF16) && (REM == 4 || REM == 2);
         const int share_piece = NPD - REM + (SHARE_LAST ? (wave * REM) / 8 : 0);
         const unsigned long long share_mask = REM == 4 ? (0xffffffffull << (32 * (wave & 1))) : (0xffffull << (16 * (wave & 3)));
         auto issue_piece = [&](int i) {
@@ -327,7 +299,7 @@ void mlp_bwd_dw_kernel(DwJobTable jobs, float* __restrict__ slabs) {
         // the top of the iteration — all 8 waves at once — they are 32-36 KiB through the CU's 64 B/clk texture-address path:
         // tools/dw_probe.py measured 0.35 us of every 1.5 us iteration in that block, 0.27 us at the barrier behind it and no time
         // at all waiting for data.  One DMA every DMA_STEP MFMAs hides the path's back-pressure under the other wave's MFMAs.
-        constexpr bool SPREAD = (PREC == NERFHIP_BF16) && NERFHIP_DW_SPREAD;
+        constexpr bool SPREAD = (PREC == NERFHIP_BF16);
         constexpr int DMA_STEP = (2 * NXT) / LPW > 0 ? (2 * NXT) / LPW : 1;
         if constexpr (REGEN) {                    // stage 0's depths lead the queue
             next_z(0);
@@ -362,7 +334,7 @@ void mlp_bwd_dw_kernel(DwJobTable jobs, float* __restrict__ slabs) {
             const char* st_base = ring + s_use * STAGE;
             s_use = (s_use + 1 == D) ? 0 : s_use + 1;
             if constexpr (SPLIT2D) {
-                constexpr int XW = NXT / 2, NF = 2 * XW, RD = NERFHIP_DW_RD2;
+                constexpr int XW = NXT / 2, NF = 2 * XW, RD = kDwFragRing2D;
                 static_assert(RD >= 2 && RD <= NF, "B fragment ring");
                 const int wi = wave >> 1, wj = wave & 1;
                 const char* dyb = st_base + (4 * wi) * SLAB_BYTES;                       // dY tiles 2 wi, 2 wi + 1
@@ -407,7 +379,7 @@ void mlp_bwd_dw_kernel(DwJobTable jobs, float* __restrict__ slabs) {
                     // the k-step boundary too (round 4: the pipeline used to drain and refill at every k-step — two exposed LDS
                     // round trips per ring stage with both waves of a SIMD in lock-step), and the bias sums (16 VALU per k-step)
                     // sit behind the first MFMAs instead of in front of them.
-                    constexpr int RD = NERFHIP_DW_RD, NM = 2 * NXT;
+                    constexpr int RD = kDwFragRing, NM = 2 * NXT;
                     const bf16x8 a0 = load_frag(dy_base, 0);
                     bf16x8 b[RD];
 #pragma unroll

@@ -32,13 +32,9 @@ struct DwF8Job {
     int x2_pair0, x2_pairs, x2_pos0;
 };
 
-#ifndef NERFHIP_DWF8_DEPTH
-#define NERFHIP_DWF8_DEPTH 4
-#endif
-
 __global__ __launch_bounds__(512, 2)
 void mlp_bwd_dw_f8_kernel(DwJobTable jobs, float* __restrict__ slabs) {
-    constexpr int DEPTH = NERFHIP_DWF8_DEPTH;
+    constexpr int DEPTH = 4;                                   // ring stages
     constexpr int MAXP = 36;                                   // pieces per stage: 2 tiles x (8 dY + 10 X) pairs
     constexpr int LPW = 5;                                     // piece DMAs per wave per stage (8 x 5 >= 36)
     constexpr int STAGE_BYTES = MAXP * kPieceBytes;
@@ -191,14 +187,14 @@ void mlp_bwd_dw_f8_kernel(DwJobTable jobs, float* __restrict__ slabs) {
                 b[0] = load_frag(x_base);
                 if (NXT > 1) b[1] = load_frag(x_base + kPieceBytes);
                 __builtin_amdgcn_sched_barrier(0);
-                accb = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, ones, accb, NERFHIP_F8_DY_E5M2, 0, 0, sa, 0, 127);   // bias: dY x 1.0
+                accb = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, ones, accb, kDyMfmaFormat, 0, 0, sa, 0, 127);   // bias: dY x 1.0
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int x = 0; x < NXT; ++x) {
                     if (x + 2 < NXT) b[(x + 2) % RD] = load_frag(x_base + (x + 2) * kPieceBytes);
                     __builtin_amdgcn_sched_barrier(0);
                     // A = dY: e5m2 (cbsz 1), B = X: e4m3 (blgp 0); lanes 0..31 carry tile T0's section scales, lanes 32..63 T1's
-                    acc[x] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b[x % RD], acc[x], NERFHIP_F8_DY_E5M2, 0, 0, sa, 0, x < x1p ? sx1 : sx2);
+                    acc[x] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b[x % RD], acc[x], kDyMfmaFormat, 0, 0, sa, 0, x < x1p ? sx1 : sx2);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else if constexpr (FOLD) {
@@ -221,10 +217,10 @@ void mlp_bwd_dw_f8_kernel(DwJobTable jobs, float* __restrict__ slabs) {
                 const i32x8 a_sg = load_frag(st_base + (np - 1) * kPieceBytes);
                 const i32x8 b0 = load_frag(xs), b1 = load_frag(xs + kPieceBytes);
                 const int sa_sg = *reinterpret_cast<const int*>(sc_base + 12), sx2 = *reinterpret_cast<const int*>(sc_base + 8);
-                acc[0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a_sg, b0, acc[0], NERFHIP_F8_DY_E5M2, 0, 0, sa_sg, 0, sx2);
-                acc[1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a_sg, b1, acc[1], NERFHIP_F8_DY_E5M2, 0, 0, sa_sg, 0, sx2);
+                acc[0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a_sg, b0, acc[0], kDyMfmaFormat, 0, 0, sa_sg, 0, sx2);
+                acc[1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a_sg, b1, acc[1], kDyMfmaFormat, 0, 0, sa_sg, 0, sx2);
                 if (wave == kDwFoldRow0)
-                    accb = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a_sg, ones, accb, NERFHIP_F8_DY_E5M2, 0, 0, sa_sg, 0, 127);
+                    accb = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a_sg, ones, accb, kDyMfmaFormat, 0, 0, sa_sg, 0, 127);
             }
 #if NERFHIP_DW_PROBE
             pr_comp += shader_cycles() - t3;

@@ -8,27 +8,16 @@
 #include "common.h"
 #include "mlp_layout.h"
 
-#ifndef NERFHIP_STORE_AUX
-#define NERFHIP_STORE_AUX 2     // cache-policy bits of the write-once stores (saved activations, dY): 2 = nt — written once, read by
-#endif                          // another kernel: -7 %, whole training step 1.65 -> 1.51 ms
-#ifndef NERFHIP_DMA_SADDR
-#define NERFHIP_DMA_SADDR 1     // weight-stream DMAs address as SGPR base + one constant per-lane VGPR offset (no per-piece VALU address)
-#endif
-#ifndef NERFHIP_DW_NT
-#define NERFHIP_DW_NT 1         // non-temporal LDS-DMA loads in the dW kernels (every byte is read once): 508 -> 466 us
-#endif
-#ifndef NERFHIP_STORE_SLACK
-#define NERFHIP_STORE_SLACK 1   // weight-ring boundaries let the stores of the last TWO chunk intervals stay in flight (0: one)
-#endif
 #ifndef NERFHIP_STREAM_PROBE
 #define NERFHIP_STREAM_PROBE 0  // debug builds: the activation-saving forward / the backward chain record the time their waves spend at
 #endif                          // the weight ring's s_waitcnt and s_barrier (results of the launch are invalid; tools/stream_probe.py)
-#ifndef NERFHIP_EXP
-#define NERFHIP_EXP 0           // timing experiments of the forward's weight ring only (results invalid), see RingStream::at_piece
-#endif
 
 namespace nerfhip {
 using namespace mlp;
+
+// cache-policy bits of the write-once stores (saved activations, dY): 2 = nt — written once, read by another kernel: -7 %, whole
+// training step 1.65 -> 1.51 ms
+constexpr int kStoreAux = 2;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -76,16 +65,8 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 // ---- global -> LDS DMA ------------------------------------------------------------------------------------------------------------
-// one 16-byte-per-lane global->LDS DMA; LDS destination = wave-uniform `lds_dst` + lane*16
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-// the same with the source as wave-uniform base (SGPR pair) + per-lane byte offset `voff`
+// one 16-byte-per-lane global->LDS DMA; LDS destination = wave-uniform `lds_dst` + lane*16; source = wave-uniform base (SGPR pair) +
+// per-lane byte offset `voff`
 __device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsigned lds_dst) {
     unsigned keep;
     asm volatile(
@@ -94,18 +75,14 @@ __device__ __forceinline__ void glds16_s(const void* sbase, unsigned voff, unsig
         : "v"(voff), "s"(sbase), "s"(lds_dst)
         : "memory");
 }
-// glds16, non-temporal: for streams every byte of which is read once (the dW kernels' dY / X slabs)
+// the same from a per-lane address, non-temporal: for streams every byte of which is read once (the dW kernels' dY / X slabs: 508 -> 466 us)
 __device__ __forceinline__ void glds16_nt(const void* gsrc, unsigned lds_dst) {
-#if NERFHIP_DW_NT
     unsigned keep;
     asm volatile(
         "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
         : "=&s"(keep)
         : "v"(gsrc), "s"(lds_dst)
         : "memory");
-#else
-    glds16(gsrc, lds_dst);
-#endif
 }
 // the same for the lanes of `mask` only (wave-uniform): the LDS image is lane-linear, so the other lanes' 16-byte units are simply not
 // fetched; the instruction still counts once in vmcnt
@@ -162,8 +139,8 @@ template <int NW_, int NCH_, bool COUNT_STORES>
 struct RingStream {
     static constexpr int NW = NW_, NCH = NCH_;
     static constexpr int LPW = kChunkPieces / NW;   // DMA instructions per wave per chunk
-    const uint8_t* gsrc;     // packed + lane*16 | NERFHIP_DMA_SADDR: packed (wave-uniform)
-    unsigned voff;           // NERFHIP_DMA_SADDR: lane*16
+    const uint8_t* gsrc;     // the packed stream (wave-uniform: an SGPR base, no per-piece VALU address)
+    unsigned voff;           // lane*16, the one constant per-lane VGPR offset of every DMA
     unsigned lds_base;       // LDS byte address of the ring
     int wave;                // wave index in the workgroup (SGPR)
     int pending;             // vector-memory STORE instructions issued since the last boundary (COUNT_STORES).
@@ -175,13 +152,8 @@ struct RingStream {
 
     __device__ __forceinline__ void issue_piece(int c, int k) const {      // k-th of this wave's LPW pieces of chunk c
         const int piece = wave + k * NW;
-#if NERFHIP_DMA_SADDR
         glds16_s(gsrc + ((size_t)c * kChunkPieces + piece) * kPieceBytes, voff,
                  lds_base + (unsigned)((c % kSlots) * kChunkBytes + piece * kPieceBytes));
-#else
-        glds16(gsrc + ((size_t)c * kChunkPieces + piece) * kPieceBytes,
-               lds_base + (unsigned)((c % kSlots) * kChunkBytes + piece * kPieceBytes));
-#endif
     }
     __device__ __forceinline__ void issue_chunk(int c) const {
 #pragma unroll
@@ -193,15 +165,7 @@ struct RingStream {
     // SLOWER: 203 vs 184 us forward, and 3x on the 4-wave SAVE variant; the burst stays.)
     template <int G>
     __device__ __forceinline__ void at_piece() {
-        if constexpr (G % kChunkPieces == 0) {
-#if NERFHIP_EXP == 1          // timing experiment only (results invalid): barriers kept, no refill DMAs after the prologue
-            wait_vm_barrier<0>();
-#elif NERFHIP_EXP == 2        // timing experiment only: neither barriers nor refills (pure MFMA + LDS reads + epilogues)
-            wait_vm<0>();
-#else
-            boundary(G / kChunkPieces);
-#endif
-        }
+        if constexpr (G % kChunkPieces == 0) boundary(G / kChunkPieces);
     }
     // Called by every wave right before the first piece of chunk c is read.
     __device__ __forceinline__ void boundary(int c) {
@@ -215,7 +179,7 @@ struct RingStream {
             // chunk c's DMAs were issued at boundary c-2; younger than them are the stores of the interval before the previous
             // boundary (pending_prev), chunk c+1's DMAs and the stores since the previous boundary (pending) => stores get two
             // chunk intervals to retire before a boundary waits for them
-            const int n = (c + 1 < NCH ? LPW : 0) + pending + (NERFHIP_STORE_SLACK ? pending_prev : 0);
+            const int n = (c + 1 < NCH ? LPW : 0) + pending + pending_prev;
             pending_prev = pending;
             pending = 0;
 #if NERFHIP_STREAM_PROBE
@@ -249,7 +213,7 @@ __device__ __forceinline__ void store_slab_b128(int& pending, __amdgpu_buffer_rs
     const u32x4* src = reinterpret_cast<const u32x4*>(&s);
 #pragma unroll
     for (int q = 0; q < (int)(sizeof(Slab) / 16); ++q) {
-        __builtin_amdgcn_raw_buffer_store_b128(src[q], rsrc, off + 16 * q, 0, NERFHIP_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(src[q], rsrc, off + 16 * q, 0, kStoreAux);
         pending += 1;
     }
 }

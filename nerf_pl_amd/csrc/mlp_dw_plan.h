@@ -1,19 +1,14 @@
 // The split plan of the weight-gradient launch: which workgroup = which (job, point range).  Host-only C++ — plain integer
 // arithmetic over mlp_layout.h's job list, compiled into the C ABI (mlp_bwd.hip) and, by a plain g++, into tests/host/dw_plan_check.cpp.
 #pragma once
-#include <stdlib.h>
-
 #include "mlp_bwd_dw.h"
 
 constexpr int kPlanF32 = 0, kPlanBf16 = 1, kPlanBf16F8 = 2;      // dtype codes: NERFHIP_F32 / _BF16 / _BF16_F8 of include/nerfhip.h
 
-#ifndef NERFHIP_DW_WGS
-#define NERFHIP_DW_WGS 512       // target workgroup count of the fp32 dW launch (2 rounds of 256 CUs at 1 workgroup/CU)
-#endif
-#ifndef NERFHIP_DWBF16_WGS
-#define NERFHIP_DWBF16_WGS 256   // bf16: ONE round.  With the pipelined inner loop the kernel itself is as fast in one round as in two
-#endif                           // (585 vs 591 us merged), and every workgroup less is a 330 KB partial slab not written and not
-                                 // re-read by the reduce: the bf16 step 1.265 -> 1.196 ms on the same box
+// Target workgroup count of the dW launch.  fp32: 2 rounds of 256 CUs at 1 workgroup/CU.  bf16: ONE round — with the pipelined inner
+// loop the kernel itself is as fast in one round as in two (585 vs 591 us merged), and every workgroup less is a 330 KB partial slab
+// not written and not re-read by the reduce: the bf16 step 1.265 -> 1.196 ms on the same box.  e4m3: one round too, see below.
+constexpr int kDwWgsF32 = 512, kDwWgsBf16 = 256, kDwWgsF8 = 256;
 
 // 32-point wave tiles of n_points, padded to whole workgroups of the forward (8 waves; fp32: 4)
 static int64_t act_tiles(int64_t n_points, int dtype) {
@@ -31,9 +26,6 @@ static int64_t act_tiles(int64_t n_points, int dtype) {
 // Several models in one launch (a training step's fine + coarse network): the workgroups are shared out ACROSS the models — a model
 // with a third of the points gets a third of the splits per job — instead of a second, short launch that cannot hide its pipeline
 // fill (coarse pass alone: 0.49 of the HBM peak vs 0.62 for the fine pass).
-#ifndef NERFHIP_DWF8_WGS
-#define NERFHIP_DWF8_WGS 256
-#endif
 // Round 4: with the inner loops pipelined (round 3) an iteration's time DOES follow its bytes — per-workgroup wall clocks of the
 // merged bf16 launch (tools/dw_probe.py, profiles/r04_dw_probe_call14_block_issue.txt): 0.69 / 0.91 / 0.82 / 1.05 / 1.40 / 1.63 us per iteration for
 // stages of 10 / 18 / 20 / 26 / 32 / 36 KiB, i.e. ~0.3 us + 35 ns per KiB.  With equal iteration counts the skip-layer workgroups
@@ -47,61 +39,41 @@ static int64_t act_tiles(int64_t n_points, int dtype) {
 // Round 6: with the 2 x 4 wave split, the dot2 bias sums and the register-major epilogue an iteration's fixed part shrank; the sweep of
 // profiles/r06_dw_plan_cost_ab.txt (one box, three alternating rounds) has 150 + 45 / KiB at 449-452 us in the step against 466-469 us for
 // round 4's 300 + 35 / KiB, 100 + 50 the same, 50 + 55 and 0 + 60 (bytes-proportional) slower again.
-#ifndef NERFHIP_DW_COST_A
-#define NERFHIP_DW_COST_A 150
-#endif
-#ifndef NERFHIP_DW_COST_B
-#define NERFHIP_DW_COST_B 45
-#endif
-#ifndef NERFHIP_DW_FOLD_SIGMA
-#define NERFHIP_DW_FOLD_SIGMA 1      // the dir layer's workgroups also form the sigma head's gradient (same X section: h8 read once)
-#endif
-#ifndef NERFHIP_DW_MIN_ITERS
-#define NERFHIP_DW_MIN_ITERS 48      // a workgroup should run at least this many ring iterations: the DEPTH-stage DMA pipeline
-#endif                               // takes ~4 to fill, and every split costs a 330 KB partial slab the reduce kernel re-reads
-static int dw_target_wgs(int dtype) {
-    static const int env = [] {
-        const char* e = getenv("NERFHIP_DW_WGS");            // experiments only
-        return e ? atoi(e) : 0;
-    }();
-    return env > 0 ? env : (dtype == kPlanBf16F8 ? NERFHIP_DWF8_WGS : dtype == kPlanBf16 ? NERFHIP_DWBF16_WGS : NERFHIP_DW_WGS);
-}
+constexpr int kDwCostA = 150, kDwCostB = 45;      // bf16: ns per ring iteration = kDwCostA + kDwCostB x (KiB of a stage)
+// a workgroup should run at least this many ring iterations: the DEPTH-stage DMA pipeline takes ~4 to fill, and every split costs a
+// 330 KB partial slab the reduce kernel re-reads
+constexpr int kDwMinIters = 48;
+static int dw_target_wgs(int dtype) { return dtype == kPlanBf16F8 ? kDwWgsF8 : dtype == kPlanBf16 ? kDwWgsBf16 : kDwWgsF32; }
 // n_points[m] points of model m (m < n_models).  Fills jt (nsplit, soff, job, ntiles, njobs; the tensor pointers are the
-// caller's) when non-null; returns the number of workgroups = partial slabs.
-static int dw_plan(const int64_t* n_points, int n_models, int dtype, nerfhip::DwJobTable* jt, const bool* regen = nullptr) {
+// caller's) when non-null; returns the number of workgroups = partial slabs.  The plan depends on these arguments alone — not on
+// whether the launch regenerates the encodings (nerfhip_mlp_bwd_multi_rays): both forms run the same workgroups, hence the same fp32
+// summation order and bit-identical gradients, and the size query (nerfhip_mlp_dw_workspace_bytes_multi) sizes what the launch uses.
+static int dw_plan(const int64_t* n_points, int n_models, int dtype, nerfhip::DwJobTable* jt) {
     using namespace nerfhip;
     using namespace nerfhip::mlp;
     const int njobs = n_models * kNumDwJobs;
     int64_t units[kDwMaxJobs];     // ring iterations of a job if it were one workgroup (f8: tile PAIRS)
     int64_t cap[kDwMaxJobs];
     int ns[kDwMaxJobs];
-    int64_t cost[kDwMaxJobs];      // time of one ring iteration of the job (ns): cost_a + cost_b x (dY + X slabs of a stage)
+    int64_t cost[kDwMaxJobs];      // time of one ring iteration of the job (ns): kDwCostA + kDwCostB x (dY + X slabs of a stage)
     int total = 0;
-    static const int cost_a = [] { const char* e = getenv("NERFHIP_DW_COST_A"); return e ? atoi(e) : -1; }();   // experiments only
-    static const int cost_b = [] { const char* e = getenv("NERFHIP_DW_COST_B"); return e ? atoi(e) : -1; }();
     for (int j = 0; j < njobs; ++j) {
         const int64_t tiles = act_tiles(n_points[j / kNumDwJobs], dtype);
         const DwJob& jb = kDwJobs[j % kNumDwJobs];
         // (the e4m3 launch keeps equal iteration counts: with the byte-weighted plan it measured 336 us against 254 us; the fp32
-        // launch has not been re-measured.  NERFHIP_DW_COST_A / _B = a + b x KiB instead, for experiments)
-        const int ca = cost_a >= 0 ? cost_a : (dtype == kPlanBf16 ? NERFHIP_DW_COST_A : 1);
-        const int cb = cost_b >= 0 ? cost_b : (dtype == kPlanBf16 ? NERFHIP_DW_COST_B : 0);
-        const bool fold = NERFHIP_DW_FOLD_SIGMA;             // (bf16 since round 4; e4m3 and fp32 since round 5; into the dir job since round 6)
-        // (regen[m]: model m's encoding sections — x1 of the first, the skip and the dir layer — are formed in the kernel, not fetched.
-        // NERFHIP_DW_REGEN_PLAN=1 prices those jobs by the bytes they still fetch; by default the plan is the one of the saved
-        // encodings — the same workgroups, hence the same fp32 summation order and bit-identical gradients in both forms — and the
-        // three job classes simply finish early)
-        static const bool regen_plan = [] { const char* e = getenv("NERFHIP_DW_REGEN_PLAN"); return e && atoi(e) != 0; }();
-        const int enc_fetched = (regen_plan && regen && regen[j / kNumDwJobs] && jb.x1_enc != 0) ? jb.x1_slabs : 0;
-        cost[j] = ca + (int64_t)cb * (jb.dy_slabs + jb.x1_slabs + jb.x2_slabs - enc_fetched + (fold && j % kNumDwJobs == kDwJobDir ? 2 : 0));
-        if (cost[j] < 1) cost[j] = 1;
+        // launch has not been re-measured)
+        const int ca = dtype == kPlanBf16 ? kDwCostA : 1;
+        const int cb = dtype == kPlanBf16 ? kDwCostB : 0;
+        // the sigma head's 2 dY slabs ride in the dir job's stage: the dir layer's workgroups also form the sigma head's gradient (same
+        // X section: h8 read once; bf16 since round 4, e4m3 and fp32 since round 5, into the dir job since round 6).  (With the
+        // encodings regenerated the first, skip and dir jobs fetch less than they are priced for and simply finish early.)
+        cost[j] = ca + (int64_t)cb * (jb.dy_slabs + jb.x1_slabs + jb.x2_slabs + (j % kNumDwJobs == kDwJobDir ? 2 : 0));
         units[j] = tiles / (dtype == kPlanBf16F8 ? 2 : 1);
-        cap[j] = NERFHIP_DW_MIN_ITERS > 0 ? units[j] / NERFHIP_DW_MIN_ITERS : units[j];
-        if (cap[j] > units[j]) cap[j] = units[j];
+        cap[j] = units[j] / kDwMinIters;
         if (cap[j] < 1) cap[j] = 1;
         // no workgroups of their own: the final layer (derived from the dir job's G by mlp_bwd_fold_kernel, mlp_layout.h kDwJobs) and,
         // folded, the sigma head (the dir layer's workgroups form dW_sigma too)
-        if (j % kNumDwJobs == kDwJobFinal || (fold && j % kNumDwJobs == kDwJobSigma)) {
+        if (j % kNumDwJobs == kDwJobFinal || j % kNumDwJobs == kDwJobSigma) {
             cap[j] = 0;
             ns[j] = 0;
             continue;

@@ -18,14 +18,17 @@
 #include "f8_store.h"
 #include "sampling_math.h"
 
-#ifndef NERFHIP_FAST_SINCOS
-#define NERFHIP_FAST_SINCOS 1   // bf16 kernels only; the fp32 (parity) kernels always use sincosf
-#endif
-#ifndef NERFHIP_PF2
-#define NERFHIP_PF2 2      // prefetch depth of the 2-waves-per-SIMD (256-register) bf16 kernels
-#endif
+#ifndef NERFHIP_CLOCK_PROBE
+#define NERFHIP_CLOCK_PROBE 0      // debug builds: every wave of the e4m3 activation-saving variant records its shader-clock cycles and
+#endif                             // 100 MHz wall ticks in spare dwords of its tile's scale piece (tools/kbench.py --clock-probe)
 
 namespace nerfhip {
+
+// A-fragment / encoding-operand prefetch depth of the 2-waves-per-SIMD (256-register) bf16 kernels: inference, activation-saving
+constexpr int kPrefetchDepth = 2, kPrefetchDepthSave = 2;
+// slabs per run of back-to-back activation stores (1 = each slab as soon as it is packed; 1, 2, 4, 8 divide the 8 / 16 output slabs
+// of every saved layer; a layer's slabs stay in registers as the next layer's operands, so holding a run back costs no register)
+constexpr int kSaveBurst = 1;
 
 // ---- training: save B-operand slabs in register (fragment) order, one coalesced 16-B store/lane/piece ----
 // (buffer stores with soffset 0: mlp_device.h store_slab_b128)
@@ -93,21 +96,9 @@ NH_HD constexpr int layer_in_sec(int L) {       // (the dir layer runs on h8 thr
 // sections the activation-saving forward writes
 NH_HD constexpr bool layer_out_saved(int L) { return layer_out_sec(L) >= 0; }
 
-#ifndef NERFHIP_EXP_NOPS
-#define NERFHIP_EXP_NOPS 0
-#endif
-#ifndef NERFHIP_EXP_SMALL
-#define NERFHIP_EXP_SMALL 0     // code-size experiment only (results invalid): no gate words, no running maximum
-#endif
-#ifndef NERFHIP_SAVE_BURST
-#define NERFHIP_SAVE_BURST 1      // 1, 2, 4, 8: divides the 8 / 16 output slabs of every saved layer
-#endif
-#ifndef NERFHIP_PF_SAVE
-#define NERFHIP_PF_SAVE 2
-#endif
 template <int PREC, int SV, typename Slab>
 struct PipeCtx {
-    static constexpr int D = (PREC != NERFHIP_BF16) ? 1 : (SV != 0 ? NERFHIP_PF_SAVE : NERFHIP_PF2);
+    static constexpr int D = (PREC != NERFHIP_BF16) ? 1 : (SV != 0 ? kPrefetchDepthSave : kPrefetchDepth);
     Slab a[D];        // A-fragment ring
     Slab bq[D];       // encoding-operand ring (slots of fragments whose B operand is an encoding slab)
     f32x16 acc[2];
@@ -155,8 +146,8 @@ __device__ __forceinline__ void epi_piece(Ctx& cx, St& st, const f32x16& c, Slab
         }
         o[2 * (p & 3)] = pk[0];
         o[2 * (p & 3) + 1] = pk[1];
-        if (SAVE && RELU && !NERFHIP_EXP_SMALL) gw = gate_shift_in(gw, __builtin_bit_cast(unsigned, pk));
-        if (F8 && !NERFHIP_EXP_SMALL) {       // running maximum of the STORED magnitudes: non-negative bf16 halves order like unsigned integers
+        if (SAVE && RELU) gw = gate_shift_in(gw, __builtin_bit_cast(unsigned, pk));
+        if (F8) {       // running maximum of the STORED magnitudes: non-negative bf16 halves order like unsigned integers
             unsigned d = __builtin_bit_cast(unsigned, pk);
             if (!RELU) d &= 0x7fff7fffu;
             cx.mx = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2v, cx.mx), __builtin_bit_cast(u16x2v, d)));
@@ -177,12 +168,10 @@ __device__ __forceinline__ void epi_piece(Ctx& cx, St& st, const f32x16& c, Slab
     }
     if constexpr (SAVE) {
         const int lane = fresh_lane();
-        // NERFHIP_SAVE_BURST slabs per run of back-to-back stores (1 = each slab as soon as it is packed; a layer's slabs stay in
-        // registers as the next layer's operands, so holding a run back costs no register)
         if (!F8 && layer_out_saved(PL) && (p & 3) == 3) {
             const int si = 2 * pt + (p >> 2);
-            if ((si + 1) % NERFHIP_SAVE_BURST == 0)
-                save_slabs<PREC>(st.pending, cx.tile, layer_out_sec(PL) + si + 1 - NERFHIP_SAVE_BURST, &po[si + 1 - NERFHIP_SAVE_BURST], NERFHIP_SAVE_BURST, lane);
+            if ((si + 1) % kSaveBurst == 0)
+                save_slabs<PREC>(st.pending, cx.tile, layer_out_sec(PL) + si + 1 - kSaveBurst, &po[si + 1 - kSaveBurst], kSaveBurst, lane);
         }
         if (RELU && p == 7 && (pt & 1)) {
             __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(cx.gate_base + layer_gate_piece(PL) * kPieceBytes * act_il(PREC, F8), 0,
@@ -313,9 +302,6 @@ __device__ __forceinline__ void run_layer_pipe(Ctx& cx, St& st, const Slab* chai
                 }
             }
         }
-#if NERFHIP_EXP_NOPS      // code-size experiment only: pad every MFMA step with s_nop (tools: slow-box instruction-cache probe)
-        static_for<0, NERFHIP_EXP_NOPS>([&](auto) { asm volatile("s_nop 0"); });
-#endif
         __builtin_amdgcn_sched_barrier(0);
     });
 }
@@ -329,7 +315,7 @@ __device__ __forceinline__ void encode_slots(const float (&v)[3], int h, Slab* o
     float vs[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) vs[c] = h ? 2.0f * v[c] : v[c];
-    if constexpr (sizeof(Slab) == 16 && NERFHIP_FAST_SINCOS) {
+    if constexpr (sizeof(Slab) == 16) {
         // bf16 kernels: hardware v_sin_f32 / v_cos_f32 (argument in REVOLUTIONS) instead of libm's sincosf, whose
         // inlined Payne-Hanek path is ~80 instructions x 42 calls per lane.  x/2pi is formed once per channel as a
         // hi+lo pair (two-constant product), scaled by the exact power of two and reduced with v_fract before the lo
@@ -349,7 +335,7 @@ __device__ __forceinline__ void encode_slots(const float (&v)[3], int h, Slab* o
             slots[2 * p] = __builtin_amdgcn_sinf(t);
             slots[2 * p + 1] = __builtin_amdgcn_cosf(t);
         }
-    } else {
+    } else {      // the fp32 (parity) kernels always use sincosf
 #pragma unroll
         for (int p = 0; p < NPAIR; ++p) {
             const int i = p / 3, c = p % 3;
@@ -420,9 +406,6 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
     char* const ring = lds_all + kBiasArea;
     char* const stash_area = ring + kSlots * kChunkBytes;
 
-#ifndef NERFHIP_CLOCK_PROBE
-#define NERFHIP_CLOCK_PROBE 0      // debug builds: every wave of the e4m3 activation-saving variant records its shader-clock cycles and
-#endif                             // 100 MHz wall ticks in spare dwords of its tile's scale piece (tools/kbench.py --clock-probe)
 #if NERFHIP_CLOCK_PROBE
     const uint64_t probe_c0 = clock64(), probe_w0 = wall_clock64();
 #endif
@@ -461,11 +444,7 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
     }
 
     RingStream<NW, NCH, SAVE> st;
-#if NERFHIP_DMA_SADDR
     st.gsrc = packed;
-#else
-    st.gsrc = packed + lane * 16;
-#endif
     st.voff = (unsigned)lane * 16u;
     st.lds_base = (unsigned)(uintptr_t)ring;
     st.wave = wave;
@@ -473,14 +452,8 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
     st.pending_prev = 0;
     // wave-uniform base of this wave's activation block (SAVE); the store helpers derive descriptors from it
     constexpr int IL = act_il(PREC, F8);    // the saved block's pieces are IL KiB apart (mlp_layout.h: bf16 slabs 8, otherwise 1)
-#ifdef NERFHIP_EXP_TILEWRAP    // timing experiment only (results invalid): every wave stores into one of a few L2-resident tile blocks
-    uint8_t* tile_base = SAVE ? save + tile_block_off((long long)(((size_t)blk * NW + wave) & (NERFHIP_EXP_TILEWRAP - 1)),
-                                                      F8 ? f8_act_tile_bytes() : act_tile_bytes(PREC), IL)
-                              : (uint8_t*)nullptr;
-#else
     uint8_t* tile_base = SAVE ? save + tile_block_off((long long)blk * NW + wave, F8 ? f8_act_tile_bytes() : act_tile_bytes(PREC), IL)
                               : (uint8_t*)nullptr;
-#endif
 
     {
         // bias image: the bias piece of every layer this kernel runs, DMA'd once from the stream's bias block (older than
@@ -489,13 +462,8 @@ __device__ __forceinline__ void mlp_fwd_body(char* const lds_all, const unsigned
         static_for<0, NLY>([&](auto lc) {
             constexpr int Lb = decltype(lc)::value;
             if (wave == Lb % NW) {
-#if NERFHIP_DMA_SADDR
                 glds16_s(st.gsrc + (size_t)(bias_block_start(PREC) + Lb) * kPieceBytes, st.voff,
                          (unsigned)(uintptr_t)bias_area + (unsigned)(Lb * kPieceBytes));
-#else
-                glds16(st.gsrc + (size_t)(bias_block_start(PREC) + Lb) * kPieceBytes,
-                       (unsigned)(uintptr_t)bias_area + (unsigned)(Lb * kPieceBytes));
-#endif
             }
         });
     }

@@ -164,7 +164,7 @@ int main() {
             }
         CHECK((int)seen.size() == tiles * pieces, "il %d covers the buffer", il);
     }
-    CHECK(act_il(0) == 1 && act_il(1, true) == 1 && act_il(1) == NERFHIP_ACT_IL, "interleave applies to the bf16 slab blocks only");
+    CHECK(act_il(0) == 1 && act_il(1, true) == 1 && act_il(1) == kActIl, "interleave applies to the bf16 slab blocks only");
     if (fails == 0) std::printf("layout ok\n");
     return fails ? 1 : 0;
 }

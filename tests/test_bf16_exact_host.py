@@ -54,7 +54,7 @@ def test_python_index_maps_equal_the_header(tmp_path):
         "consts": [E.kXyzCh, E.kDirCh, E.kW, E.kXyzSlabs, E.kDirSlabs, E.kPieceBytes, E.kActEncX, E.kActEncD, E.kActH0, E.kActFeat, E.kActT,
                    E.kActSlabs, E.kMaskPieces, E.kMaskPieceT, E.kDyRgb, E.kDyDir, E.kDyFeat, E.kDySigma, E.kDyH0, E.kDySlabs,
                    E.act_mask_off(), E.act_tile_bytes(), E.dy_tile_bytes(), 1, E.kNumLayers, E.kSigmaLayer, E.kDirLayer,
-                   E.bias_block_start(), E.bias_block_pieces()],          # (the 1: the decoder's default il is the header's NERFHIP_ACT_IL)
+                   E.bias_block_start(), E.bias_block_pieces()],          # (the 1: the decoder's default il is the header's kActIl)
         "act_h": [E.act_h(l) for l in range(1, 9)],
         "dy_h": [E.dy_h(l) for l in range(1, 9)],
         "mask_piece_h": [l - 1 for l in range(1, 9)],
@@ -99,7 +99,7 @@ def test_encode_decode_identity_and_every_byte_accounted_for():
         assert torch.equal(dd[k], v), k
     # a second encoding of what was decoded is the same bytes (the maps are bijections onto the claimed bytes)
     assert torch.equal(E.encode_acts(da, tiles), ba) and torch.equal(E.encode_dys(dd, tiles), bd)
-    # the interleaved block addressing (NERFHIP_ACT_IL = 8) holds the same pieces elsewhere
+    # the interleaved block addressing (kActIl = 8) holds the same pieces elsewhere
     il, per = 8, E.act_tile_bytes() // E.kPieceBytes
     src = E.encode_acts({k: torch.cat([v] * 3)[:32 * 8] for k, v in acts.items()}, 8).numpy().reshape(8, per, E.kPieceBytes)
     inter = np.zeros(8 * E.act_tile_bytes(), dtype=np.uint8)

@@ -79,6 +79,15 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in txt.replace("no oracle", ""), os.path.join(dp, f)
 
 
+def test_library_reads_no_environment():
+    """What libnerfhip computes is a function of its arguments: no source under csrc/ asks the loading process's environment."""
+    csrc = os.path.join(ROOT, "nerf_pl_amd", "csrc")
+    files = [os.path.join(dp, f) for dp, _, fs in os.walk(csrc) for f in fs]
+    assert files
+    for path in files:
+        assert "getenv" not in open(path, errors="replace").read(), path
+
+
 def test_install_registers_reference_module_names():
     """nerf_pl_amd.install() makes the reference's imports (train.py:10-11, eval.py:9-10, rendering.py:2) resolve here."""
     import importlib

@@ -41,7 +41,7 @@ def test_benchmark_step_is_one_round_of_the_256_cus(lib):
 
 def iter_cost(kib):
     """Round 6 cost model of one ring iteration of the bf16 kernel, in ns: 150 + 45 per KiB of its stage (csrc/mlp_dw_plan.h
-    NERFHIP_DW_COST_A/B; sweep in profiles/r06_dw_plan_cost_ab.txt).  Round 4's kernel measured 0.7-1.8 us per iteration
+    kDwCostA / kDwCostB; sweep in profiles/r06_dw_plan_cost_ab.txt).  Round 4's kernel measured 0.7-1.8 us per iteration
     (tools/dw_probe.py) and planned with 300 + 35 per KiB; the 2 x 4 wave split, dot2 bias sums and register-major epilogue of
     round 6 shrank the fixed part, and the sweep then preferred a plan nearer to bytes-proportional."""
     return 150 + 45 * kib
