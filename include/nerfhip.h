@@ -37,8 +37,9 @@ extern "C" {
 #define NERFHIP_F32 0  /* v_mfma_f32_32x32x2_f32, exact fp32 (parity configuration)      */
 #define NERFHIP_BF16 1 /* v_mfma_f32_32x32x16_bf16, fp32 accumulate (roofline config)    */
 #define NERFHIP_BF16_F8 2 /* as NERFHIP_BF16 (forward, dX chain: bf16 MFMA); the tensors saved for the weight-gradient
-                           * GEMM (activations X, dY) are stored as block-scaled OCP e4m3 (one e8m0 scale per 32 points x
-                           * 32 features) and consumed by v_mfma_scale_f32_32x32x64_f8f6f4: half the backward's HBM bytes.
+                           * GEMM are stored block-scaled in 8 bits — the activations X as OCP e4m3, dY as OCP e5m2, one
+                           * e8m0 scale per 32 points x one layer's section — and consumed by
+                           * v_mfma_scale_f32_32x32x64_f8f6f4: half the backward's HBM bytes.
                            * Inference entry points treat it as NERFHIP_BF16.                                          */
 
 typedef void* nerfhip_stream_t;

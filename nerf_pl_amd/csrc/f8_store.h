@@ -1,4 +1,4 @@
-// fp8 (OCP e4m3, block-scaled) storage of the tensors saved for the weight-gradient GEMM — shared by the activation-saving
+// fp8 (block-scaled OCP e4m3 for X, e5m2 for dY) storage of the tensors saved for the weight-gradient GEMM — shared by the activation-saving
 // forward (mlp_fwd_kernel.h) and the backward chain (mlp_bwd_chain.hip).  Format: mlp_layout.h "fp8 storage of the saved tensors".
 #pragma once
 #include "mlp_device.h"

@@ -316,17 +316,21 @@ constexpr int kDwMaxXTiles = 10;            // (4+16)/2
 constexpr int kDwSlabFloats = 8 * kDwMaxXTiles * 64 * 16 + 8 * 64;
 
 // ================================================================================================
-// fp8 storage of the saved tensors (dtype NERFHIP_BF16_F8): bf16 MFMA chain, e4m3 dW operands
+// fp8 storage of the saved tensors (dtype NERFHIP_BF16_F8): bf16 MFMA chain, 8-bit dW operands (X: e4m3, dY: e5m2)
 // ================================================================================================
 // The dW GEMM (points = K) is the only consumer of the saved activations X and of dY, and it is bound by the bytes it
 // reads.  In this mode the activation-saving forward and the backward chain store every slab PAIR (2t, 2t+1) — the 32
-// features of one MFMA operand tile, 32 points — as ONE 1 KiB piece of OCP e4m3 bytes, lane (n, h) holding
+// features of one MFMA operand tile, 32 points — as ONE 1 KiB piece of 8-bit codes, lane (n, h) holding
 // [slab 2t: 8 B | slab 2t+1: 8 B] — the operand format of v_mfma_scale_f32_32x32x64_f8f6f4, whose 32-wide K blocks are
-// exactly the 32 points of a wave tile:
-// OCP e4m3 with one e8m0 scale byte per (wave tile, 16-slab section = one layer's activations or dY):
-//      stored q = x / 2^(E-127), E = max(Emax - 7, 1), Emax = biased exponent of the block's max |x|
-//      => |q| < 2^8 <= 448 (e4m3 max; v_cvt_scalef32_pk_fp8 does not saturate, it produces NaN above 464).
-// The input encodings (|sin|, |cos| <= 1, coordinates << 448) use the fixed scale 2^0.
+// exactly the 32 points of a wave tile — with one e8m0 scale byte E per (wave tile, section = one layer's activations or dY),
+// stored q = x / 2^(E-127), rounded to nearest even:
+//   X (activations, encodings): OCP e4m3.  E = max(Emax - 7, 1), Emax = biased exponent of the largest STORED bf16 |x| of the
+//      section => |q| < 2^8 <= 448 (e4m3 max; v_cvt_scalef32_pk_fp8 does not saturate, it produces NaN above 464).
+//      The input encodings (|sin|, |cos| <= 1, coordinates << 448) use the fixed scale 2^0 (E = 127).
+//   dY: OCP e5m2 (f8_store.h kDyMfmaFormat, save_pair_bf8).  E = max(Emax - 14, 1), Emax taken from the chain's UNGATED fp32
+//      accumulators before the bf16 rounding => |q| <= 2^15 < 57344 (e5m2 max; exactly 2^15 where a value just under a power of
+//      two rounds up to it in bf16); the rgb / sigma seeds take Emax from their bf16 slabs.
+// oracle/f8_exact.py restates this section in Python; tests/test_gpu_f8_exact.py checks both kernels against it bit for bit.
 // Tile block of X:  [79 pair pieces][9 gate pieces (as before)][1 KiB: scale dwords, one per SECTION at f8_x_section()]
 // Tile block of dY: [78 pair pieces][1 KiB: scale dwords, one per SECTION at f8_dy_section()]
 constexpr int kF8ActPairs = kActSlabs / 2;          // 79

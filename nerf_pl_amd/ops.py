@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import BF16, BF16_F8, F32, NerfHipError, check, device_guard, ptr, require_gpu, stream_ptr
 
 # 'bf16_f8': bf16 MFMA forward and dX chain; the tensors saved for the weight-gradient GEMM (activations, dY) are stored
-# as block-scaled e4m3 and consumed by the MX-scaled fp8 MFMA (include/nerfhip.h: NERFHIP_BF16_F8)
+# block-scaled in 8 bits (activations: e4m3, dY: e5m2) and consumed by the MX-scaled fp8 MFMA (include/nerfhip.h: NERFHIP_BF16_F8)
 _DTYPES = {"fp32": F32, "f32": F32, "float32": F32, torch.float32: F32, F32: F32,
            "bf16": BF16, "bfloat16": BF16, torch.bfloat16: BF16, "bf16_f8": BF16_F8}
 

@@ -9,7 +9,8 @@ Every configuration starts from the same default-init weights and consumes the s
 
 These gates compare with the fp32 oracle and therefore allow the bf16 rounding itself (10 % of a gradient tensor).  Exactness of
 the bf16 kernels — every layer, chain layer and weight-gradient job against a model that rounds where they round — is
-tests/test_gpu_bf16_exact.py (model and decoder: oracle/bf16_exact.py, tests/test_bf16_exact_host.py)."""
+tests/test_gpu_bf16_exact.py (model and decoder: oracle/bf16_exact.py, tests/test_bf16_exact_host.py); the fp8-storage mode's codes,
+scales and weight-gradient kernel are tests/test_gpu_f8_exact.py (oracle/f8_exact.py, tests/test_f8_exact_host.py)."""
 from argparse import Namespace
 
 import pytest

@@ -25,7 +25,7 @@ def _oracle_param_grads(p, x, g_out):
 def test_mlp_backward_embedded_vs_autograd(dev, dtype, tol, n):
     """Forward and the 24 gradients of the fused MLP against autograd through the fp32 oracle.  For the reduced-precision modes this
     is a direction gate that has to allow the bf16 rounding; what the bf16 kernels compute EXACTLY, stage by stage on the same inputs,
-    is pinned by tests/test_gpu_bf16_exact.py."""
+    is pinned by tests/test_gpu_bf16_exact.py; the 8-bit storage of 'bf16_f8' and its dW kernel by tests/test_gpu_f8_exact.py."""
     g = torch.Generator().manual_seed(n)
     p = O.make_params(21, 3.0, 0.1)
     pts = torch.rand(n, 3, generator=g) * 4 - 2
@@ -60,8 +60,9 @@ def test_mlp_backward_embedded_vs_autograd(dev, dtype, tol, n):
 
 
 def test_f8_storage_gradients_track_bf16(dev):
-    """The fp8-storage mode changes only the operands of the weight-gradient GEMM (e4m3, one power-of-two scale per 32 points
-    x 32 features): forward output identical to bf16, every gradient tensor within a few % (relative L2) of the bf16 one."""
+    """The fp8-storage mode changes only the operands of the weight-gradient GEMM (X as e4m3, dY as e5m2, one power-of-two scale
+    per 32 points x one layer's section): forward output identical to bf16, every gradient tensor within a few % (relative L2) of
+    the bf16 one.  What is stored, bit for bit, and what the dW kernel makes of it: tests/test_gpu_f8_exact.py."""
     n = 3000
     g = torch.Generator().manual_seed(7)
     p = O.make_params(21, 3.0, 0.1)
