@@ -600,6 +600,34 @@ int nerfhip_jpeg_decode(const int16_t* coef_y, const int16_t* coef_cb, const int
                         uint8_t* planes, uint8_t* out, int n_images, int H, int W, int n_comp, int hs, int vs,
                         nerfhip_stream_t stream);
 
+/* ---- scoring and logging rendered images  (metrics.py:15-20, utils/visualization.py:6-17; DESIGN.md "Image metrics") ---------
+ * ssim: the reference's `metrics.ssim` = 1 - 2 * kornia.losses.ssim(img1, img2, window_size, reduction) as kornia 0.2.0 defines
+ * it.  Window: outer product of g[i] = exp(-(i - ws/2)^2 / (2 * 1.5^2)) normalised to sum 1; depth-wise filter with zero padding
+ * (ws - 1) / 2 (the padded zeros take part in every mean); per pixel and channel, with mu = filt(x), s11 = filt(x1^2) - mu1^2,
+ * s22 = filt(x2^2) - mu2^2, s12 = filt(x1 x2) - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2:
+ *     m = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),   value = 1 - 2 * (clamp(1 - m, 0, 1) / 2).
+ * The second moments are formed on images centred per 32 x 32 tile, so they do not cancel (flat images are exact where the
+ * reference's own fp32 arithmetic is off by up to 1.5e-3).  img1, img2: B images of C channels, H x W, `layout` planar (B,C,H,W)
+ * or interleaved (B,H,W,C) (a renderer's (H*W,3) colours: B = 1, C = 3).  map: the values in the images' layout, or NULL.
+ * mean: one DEVICE float, or NULL; deterministic (per-tile fp64 sums in `workspace`, folded in index order by a second launch).
+ * workspace: ssim_workspace_bytes(B,C,H,W) bytes, 8-byte aligned; needed for `mean` only.  window_size odd, 3..11.
+ * B*C*H*W == 0 is success; a null image with elements to read, another window_size or layout, or more than 2^31 - 1 tiles is
+ * NERFHIP_E_BADARG before anything is launched.                                                                              */
+#define NERFHIP_IMAGE_PLANAR 0
+#define NERFHIP_IMAGE_INTERLEAVED 1
+size_t nerfhip_ssim_workspace_bytes(int B, int C, int H, int W);
+int nerfhip_ssim(const float* img1, const float* img2, int B, int C, int H, int W, int window_size, int layout, float* map,
+                 float* mean, void* workspace, nerfhip_stream_t stream);
+/* visualize_depth: x = nan_to_num(depth) (NaN -> 0, +-inf -> +-FLT_MAX), mi / ma = its minimum / maximum over the n pixels (never
+ * read by the host), x = (x - mi) / (ma - mi + 1e-8f) with every operation rounded to fp32 as numpy does, index = trunc(255 x) as
+ * uint8 (a NaN quotient -> 0).  table: 256 x 3 DEVICE bytes; out_chw (3,n) float32 = table[index][k] / 255 (fp32 division, as
+ * ToTensor), out_hwc (n,3) uint8 = table[index][k]; either may be NULL.  The reference hands cv2's BGR image to PIL as RGB, so
+ * its channel 0 is the colour map's blue: a table holds a colour's bytes in OUTPUT channel order.  Two launches.
+ * workspace: depth_colormap_workspace_bytes(n) bytes, 4-byte aligned.  n == 0 is success.                                     */
+size_t nerfhip_depth_colormap_workspace_bytes(int64_t n);
+int nerfhip_depth_colormap(const float* depth, int64_t n, const uint8_t* table, float* out_chw, uint8_t* out_hwc, void* workspace,
+                           nerfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,10 +30,12 @@ def default_mlp_dtype():
     return _DEFAULT_MLP_DTYPE
 
 
-def install(datasets=False):
+def install(datasets=False, metrics=False):
     """Register this package's modules under the names the reference imports
     (train.py:10-11, eval.py:9-10, models/rendering.py:2).  datasets=True: also `datasets`, `datasets.blender` and
-    `datasets.llff` (train.py:8, eval.py:12) — off by default, so that inside a reference tree the reference's own loaders stay in charge."""
+    `datasets.llff` (train.py:8, eval.py:12) — off by default, so that inside a reference tree the reference's own loaders stay in charge.
+    metrics=True: also `metrics` (train.py:19, eval.py:15: mse, psnr, ssim) and `utils.visualization` (train.py:14) — off by default
+    for the same reason; a `utils` package that is not imported yet is registered as an empty one holding `visualization`."""
     from . import models, ops
     from .models import nerf, rendering
     sys.modules["models"] = models
@@ -47,3 +49,12 @@ def install(datasets=False):
         sys.modules["datasets"] = ds
         sys.modules["datasets.blender"] = ds.blender
         sys.modules["datasets.llff"] = ds.llff
+    if metrics:
+        from . import metrics as m, visualization
+        sys.modules["metrics"] = m
+        utils = sys.modules.get("utils")
+        if utils is None:
+            utils = sys.modules["utils"] = types.ModuleType("utils")
+            utils.__path__ = []
+        utils.visualization = visualization
+        sys.modules["utils.visualization"] = visualization

@@ -343,3 +343,14 @@ def read_pfm(filename):
 def depth_bytes(depth):
     """eval.py:135-137 (`--depth_format bytes`): the float32 depth map's raw bytes."""
     return np.ascontiguousarray(depth, dtype=np.float32).tobytes()
+
+
+def jet_table():
+    """The JET colour map as a (256, 3) uint8 table whose columns are in the order of the channels `visualize_depth` returns:
+    the reference hands cv2's BGR image to PIL as if it were RGB (visualization.py:16-17), so column 0 is the map's BLUE,
+    column 1 its green and column 2 its red.  v = (i + 1) / 256; r = clip(1.5 - |4v - 3|), g = clip(1.5 - |4v - 2|),
+    b = clip(1.5 - |4v - 1|); bytes = round-half-even(255 c).  (Formed in float64, where every value before the rounding is
+    exact.  Equality with the bytes of cv2.COLORMAP_JET is unverified: cv2 is no dependency; a table is an argument.)"""
+    v = (np.arange(256, dtype=np.float64) + 1.0) / 256.0
+    r, g, b = (np.clip(1.5 - np.abs(4.0 * v - k), 0.0, 1.0) for k in (3.0, 2.0, 1.0))
+    return np.rint(255.0 * np.stack([b, g, r], axis=1)).astype(np.uint8)

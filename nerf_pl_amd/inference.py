@@ -187,3 +187,61 @@ def save_image_outputs(results, h, w, dir_name, index, save_depth=False, depth_f
     img_pred_ = (img_pred * 255).astype(np.uint8)
     write_png(os.path.join(dir_name, "%03d.png" % index), img_pred_)
     return img_pred_
+
+
+def image_to_u8(rgb):
+    """trunc(float32(rgb * 255)) as uint8 on the device — eval.py:136 `(img_pred * 255).astype(np.uint8)` before the copy to
+    the host instead of after it: 3 bytes per pixel cross the bus instead of 12 (`nerfhip_mesh_rgb_to_u8`)."""
+    return ops.rgb_to_u8(rgb)
+
+
+@torch.no_grad()
+def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="pfm", window_size=3):
+    """The loop of the reference's eval.py (eval.py:112-149, without the gif) with its tail on the GPU.
+
+    dataset: `len`, `img_wh` = (w, h), items with 'rays' (h*w, 8) and optionally 'rgbs' (h*w, 3).  renderer: rays on the GPU ->
+    a dict with 'rgb_fine' (h*w, 3) and 'depth_fine' (h*w,) (a `GraphRenderer`, or a closure over `batched_inference`).
+    Per image: render; PSNR and SSIM against the ground truth on the device; uint8 on the device; copy the bytes to the host;
+    with `dir_name`, write `{i:03d}.png` and (save_depth) `depth_{i:03d}.pfm` / `depth_{i:03d}` as `save_image_outputs` does.
+    The metric scalars stay on the device and are read once, after the last image.
+
+    Returns {'psnr': [...], 'ssim': [...], 'mean_psnr', 'mean_ssim', 'images': [(h, w, 3) uint8 arrays]} (the lists are empty
+    and the means None for a dataset without ground truth)."""
+    import os
+
+    import numpy as np
+
+    from . import metrics
+    from .imageio_min import depth_bytes, save_pfm, write_png
+    w, h = dataset.img_wh
+    if dir_name is not None:
+        os.makedirs(dir_name, exist_ok=True)
+    images, psnrs, ssims = [], [], []
+    for i in range(len(dataset)):
+        sample = dataset[i]
+        rays = sample["rays"]
+        dev = rays.device if rays.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        results = renderer(rays.to(dev))
+        rgb = results["rgb_fine"].reshape(h * w, 3)
+        if "rgbs" in sample:
+            gt = sample["rgbs"].to(dev).reshape(h * w, 3)
+            psnrs.append(metrics.psnr(gt, rgb))                      # eval.py:143's argument order
+            ssims.append(metrics.ssim_hw3(rgb, gt, h, w, window_size=window_size))
+        img = image_to_u8(rgb).reshape(h, w, 3).cpu().numpy()
+        images.append(img)
+        if dir_name is None:
+            continue
+        if save_depth:
+            depth = np.nan_to_num(results["depth_fine"].reshape(h, w).cpu().numpy())
+            if depth_format == "pfm":
+                save_pfm(os.path.join(dir_name, "depth_%03d.pfm" % i), depth)
+            else:
+                with open(os.path.join(dir_name, "depth_%03d" % i), "wb") as f:
+                    f.write(depth_bytes(depth))
+        write_png(os.path.join(dir_name, "%03d.png" % i), img)
+    out = {"psnr": [], "ssim": [], "mean_psnr": None, "mean_ssim": None, "images": images}
+    if psnrs:
+        both = torch.stack([torch.stack(psnrs), torch.stack(ssims)]).cpu().numpy()       # the one read of the metric scalars
+        out["psnr"], out["ssim"] = both[0].tolist(), both[1].tolist()
+        out["mean_psnr"], out["mean_ssim"] = float(np.mean(out["psnr"])), float(np.mean(out["ssim"]))
+    return out

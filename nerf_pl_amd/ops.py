@@ -1045,6 +1045,59 @@ def rgb_to_u8(rgb):
     return out
 
 
+# ------------------------------------------------------------------------------- image metrics (metrics.py:15-20, visualization.py)
+IMAGE_PLANAR, IMAGE_INTERLEAVED = 0, 1
+
+
+@device_guard
+def ssim(img1, img2, B, C, H, W, window_size=3, layout=IMAGE_PLANAR, want_map=False, want_mean=True):
+    """nerfhip_ssim: 1 - 2 * dssim of kornia 0.2.0 for B images of C channels, H x W, planar (B,C,H,W) or interleaved (B,H,W,C).
+    Returns (map in the images' layout or None, mean as a 0-dim device tensor or None).  No host synchronisation."""
+    require_gpu(img1, img2)
+    B, C, H, W, window_size = int(B), int(C), int(H), int(W), int(window_size)
+    if min(B, C, H, W) < 0 or img1.numel() != B * C * H * W or img2.numel() != img1.numel():
+        raise NerfHipError("ssim: images of %s and %s elements are not %d x %d x %d x %d" % (img1.numel(), img2.numel(), B, C, H, W))
+    if window_size % 2 == 0 or not 3 <= window_size <= 11:
+        raise NerfHipError("ssim: window_size must be odd and in 3..11, got %d" % window_size)
+    img1, img2 = _c(img1), _c(img2)
+    dev = img1.device
+    lib = _lib.load()
+    shape = (B, C, H, W) if layout == IMAGE_PLANAR else (B, H, W, C)
+    out_map = torch.empty(shape, device=dev, dtype=torch.float32) if want_map else None
+    mean = ws = None
+    if want_mean:
+        mean = torch.full((), float("nan"), device=dev, dtype=torch.float32) if img1.numel() == 0 else \
+            torch.empty((), device=dev, dtype=torch.float32)
+        ws = torch.empty(max(1, lib.nerfhip_ssim_workspace_bytes(B, C, H, W) // 8), device=dev, dtype=torch.float64)
+    check(lib.nerfhip_ssim(ptr(img1), ptr(img2), B, C, H, W, window_size, int(layout), ptr(out_map), ptr(mean), ptr(ws), stream_ptr()),
+          "nerfhip_ssim")
+    return out_map, mean
+
+
+def _require_depth_table(table, device):
+    if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.uint8 or tuple(table.shape) != (256, 3) \
+            or table.device != device:
+        raise NerfHipError("depth_colormap: the colour table must be a (256, 3) uint8 tensor on %s" % (device,))
+    return _c(table)
+
+
+@device_guard
+def depth_colormap(depth, table, want_float=True, want_bytes=False):
+    """nerfhip_depth_colormap: visualize_depth of an (H, W) or (n,) depth image through a (256, 3) uint8 device table.
+    Returns (float image (3, *depth.shape) or None, byte image (*depth.shape, 3) or None).  No host read of the minimum / maximum."""
+    require_gpu(depth)
+    table = _require_depth_table(table, depth.device)
+    depth = _c(depth)
+    n, dev = depth.numel(), depth.device
+    lib = _lib.load()
+    out_f = torch.empty((3,) + tuple(depth.shape), device=dev, dtype=torch.float32) if want_float else None
+    out_b = torch.empty(tuple(depth.shape) + (3,), device=dev, dtype=torch.uint8) if want_bytes else None
+    ws = torch.empty(max(1, lib.nerfhip_depth_colormap_workspace_bytes(n) // 4), device=dev, dtype=torch.float32)
+    check(lib.nerfhip_depth_colormap(ptr(depth), n, ptr(table), ptr(out_f), ptr(out_b), ptr(ws), stream_ptr()),
+          "nerfhip_depth_colormap")
+    return out_f, out_b
+
+
 # ------------------------------------------------------------------------------- scene loading (datasets/blender.py:47-58, 90-95)
 def _require_u8(name, t):
     if not torch.is_tensor(t):

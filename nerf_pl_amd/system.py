@@ -164,13 +164,26 @@ class NeRFSystem(_Base):
         from .models.train_step import fusable
         return fusable(self.models, self.embeddings, self.loss)
 
+    def validation_panel(self, results, rgbs, H, W):
+        """train.py:127-133: the (3, 3, H, W) stack [ground truth, prediction, colour-mapped depth], built on the device."""
+        from .visualization import visualize_depth
+        typ = 'fine' if 'rgb_fine' in results else 'coarse'
+        img = results[f'rgb_{typ}'].view(H, W, 3).permute(2, 0, 1)
+        img_gt = rgbs.view(H, W, 3).permute(2, 0, 1)
+        depth = visualize_depth(results[f'depth_{typ}'].view(H, W))
+        return torch.stack([img_gt, img, depth])
+
     def validation_step(self, batch, batch_nb):
-        """train.py:119-138 (image logging omitted: harness concern)."""
+        """train.py:119-138; the image panel is logged for the first batch when a logger is attached."""
         rays, rgbs = self.decode_batch(batch)
         rays, rgbs = rays.squeeze(), rgbs.squeeze()
         results = self(rays)
         log = {'val_loss': self.loss(results, rgbs)}
         typ = 'fine' if 'rgb_fine' in results else 'coarse'
+        if batch_nb == 0 and getattr(self, 'logger', None) is not None:
+            W, H = self.hp.img_wh
+            self.logger.experiment.add_images('val/GT_pred_depth', self.validation_panel(results, rgbs, H, W),
+                                              getattr(self, 'global_step', 0))
         log['val_psnr'] = psnr(results[f'rgb_{typ}'], rgbs)
         return log
 
