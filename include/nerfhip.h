@@ -628,6 +628,36 @@ size_t nerfhip_depth_colormap_workspace_bytes(int64_t n);
 int nerfhip_depth_colormap(const float* depth, int64_t n, const uint8_t* table, float* out_chw, uint8_t* out_hwc, void* workspace,
                            nerfhip_stream_t stream);
 
+/* ---- animated GIF  (eval.py:145 `imageio.mimsave(f'{scene_name}.gif', imgs, fps=30)`) -------------------------
+ * Per frame its own 256-entry palette; all arithmetic is integer and the result is a pure function of the frames (DESIGN.md §13
+ * holds the definition, tests/gif_ref.py restates it in numpy).  F frames of H x W, 1 <= H, W <= 65535, H * W <= 2^26,
+ * 0 <= F <= 65535; F == 0 is success and touches nothing; null pointers with F > 0 and sizes outside these ranges are
+ * NERFHIP_E_BADARG before anything is launched; `workspace` is 8-byte aligned (NERFHIP_E_ALIGN) and holds
+ * gif_workspace_bytes(F, H, W) bytes (0 for a refused shape) — about 38.5 KB per strip of NERFHIP_GIF_STRIP pixels plus 168 KB per
+ * frame; both calls may share it.  Nothing is allocated, nothing synchronises.
+ *
+ * gif_quantize: frames (F,H,W,3) uint8 -> indices (F,H*W) uint8, palettes (F,256,3) uint8, box_counts (F) int32.  Histogram over
+ * the 32^3 bins (r>>3, g>>3, b>>3); median cut on it (boxes shrunk to their occupied bins; split the most populated box that
+ * spans more than one bin, tie to the lowest index, along its longest axis in bins, tie to r, g, b, after the first coordinate
+ * whose cumulative count reaches (n + 1) / 2, clamped so the upper part is not empty; the lower part keeps the index, the upper
+ * gets the next) until 256 boxes or none can be split; index = the box of the pixel's bin; palette entry = (2 sum + cnt) / (2 cnt)
+ * of the entry's true colours, unused entries 0.
+ *
+ * gif_lzw: indices (F,H*W) -> data (F, gif_data_stride(H,W)) uint8 and lengths (F) int32: per frame the image data as it stands
+ * in the file between the minimum-code-size byte (8) and the zero-length terminator: the LZW code stream (clear 256, end 257,
+ * first free code 258, 9..12 bits, LSB first) in 255-byte sub-blocks behind their length bytes.  The index stream is cut into
+ * strips of NERFHIP_GIF_STRIP consecutive pixels; each starts with a clear code, the end code follows the last.  A strip of K
+ * pixels makes its decoder assign codes up to 257 + K - 1 <= 4094, so the 4096-code table never fills and no overflow path
+ * exists.  Bytes behind lengths[f] are not written.  lengths[f] == -1: a dictionary probe exceeded its bound (a broken
+ * invariant, never input-dependent); that frame's data is not written.                                                          */
+#define NERFHIP_GIF_STRIP 3838
+size_t nerfhip_gif_workspace_bytes(int F, int H, int W);
+size_t nerfhip_gif_data_stride(int H, int W);
+int nerfhip_gif_quantize(const uint8_t* frames, int F, int H, int W, uint8_t* indices, uint8_t* palettes, int32_t* box_counts,
+                         void* workspace, nerfhip_stream_t stream);
+int nerfhip_gif_lzw(const uint8_t* indices, int F, int H, int W, uint8_t* data, int32_t* lengths, void* workspace,
+                    nerfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,13 @@
 // Mesh extraction from a sigma grid (extract_color_mesh.py:144-285): marching cubes, largest-cluster cleanup, vertex normals
 // and per-view colour fusion.  Every kernel is one thread per lattice point / triangle / vertex; the only cross-block
 // communication is the block-total scan (one workgroup) between two launches.  Layouts and byte counts: DESIGN.md, mesh.
+#include "block_scan.h"
 #include "common.h"
 #include "mc_tables.h"
 
 namespace {
+
+using nerfhip::block_excl_scan;
 
 constexpr int kBlock = 256;        // threads of every per-element kernel here (4 waves)
 constexpr int kScanBlock = 1024;   // the single workgroup that scans the block totals
@@ -20,32 +23,6 @@ __device__ __forceinline__ int tri_count(int c) {
     int n = 0;
     while (n < 5 && nerfhip::kMcTriTable[c][3 * n] >= 0) ++n;
     return n;
-}
-
-// Exclusive scan of one value per thread over a block of NT threads (NT/64 waves): returns the thread's exclusive prefix,
-// `total` gets the block's sum.  Callable once per __syncthreads-separated phase.
-template <int NT, typename T>
-__device__ __forceinline__ T block_excl_scan(T v, T& total) {
-    __shared__ T wsum[NT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        const T s = wsum[w];
-        if (w < wave) before += s;
-        all += s;
-    }
-    __syncthreads();
-    total = all;
-    return before + incl - v;
 }
 
 // ---- marching cubes -----------------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """Image / depth writers of the reference's eval loop (eval.py:119-149) without its imageio / cv2 dependencies:
 PNG (8-bit RGB or grey, zlib-deflated, filter 0), PFM (datasets/depth_utils.py:43-69 `save_pfm` / `read_pfm`, same bytes)
 and the raw little-endian float32 dump of `--depth_format bytes` (eval.py:135-137); and the host half of scene loading
-(nerf_pl_amd/datasets): the PNG container parser, the JPEG marker parser and Pillow's Lanczos taps.  Host-side, numpy only."""
+(nerf_pl_amd/datasets): the PNG container parser, the JPEG marker parser and Pillow's Lanczos taps.  Host-side, numpy only —
+except the animated GIF of eval.py:145 at the end of the file, whose palettes and LZW data come from the GPU (csrc/gif.hip)
+and whose container is written here."""
 import math
 import re
 import struct
@@ -354,3 +356,194 @@ def jet_table():
     v = (np.arange(256, dtype=np.float64) + 1.0) / 256.0
     r, g, b = (np.clip(1.5 - np.abs(4.0 * v - k), 0.0, 1.0) for k in (3.0, 2.0, 1.0))
     return np.rint(255.0 * np.stack([b, g, r], axis=1)).astype(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------- animated GIF (eval.py:145)
+GIF_BATCH = 8          # frames quantised and LZW-coded per call: at 800 x 800 about 10 MB of device memory per frame
+
+
+def _gif_header(w, h):
+    """'GIF89a', the logical screen (no global colour table) and the NETSCAPE2.0 block for endless looping."""
+    return b"GIF89a" + struct.pack("<HHBBB", w, h, 0x70, 0, 0) + b"\x21\xff\x0bNETSCAPE2.0\x03\x01\x00\x00\x00"
+
+
+def _gif_frame_header(w, h, fps):
+    """Graphic control extension (delay in centiseconds, no transparency, no disposal) and the image descriptor of a full frame
+    with a 256-entry local colour table."""
+    return b"\x21\xf9\x04\x00" + struct.pack("<H", round(100 / fps)) + b"\x00\x00\x2c" + struct.pack("<HHHHB", 0, 0, w, h, 0x87)
+
+
+class GifWriter:
+    """The file of `imageio.mimsave(path, imgs, fps=fps)` piece by piece: `append` takes (n, H, W, 3) uint8 frames ON THE
+    DEVICE, `getvalue` closes the file.  Per `append`: quantise and LZW-code on the GPU (ops.gif_quantize, ops.gif_lzw), read
+    the n lengths, then the palettes and the data up to the longest length; every frame has its own palette, as imageio's writer
+    gives it.  Nothing is kept on the device between calls."""
+
+    def __init__(self, fps=30):
+        if not fps > 0 or round(100 / fps) > 65535:
+            raise ValueError("fps must be positive and give a delay below 65536 centiseconds, got %r" % (fps,))
+        self.fps, self.size, self.pieces, self.n_frames = fps, None, [], 0
+
+    def append(self, frames):
+        from . import ops
+        from ._lib import NerfHipError
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("GifWriter.append expects (n, H, W, 3) uint8 frames, got %s" % (tuple(frames.shape),))
+        n, h, w = frames.shape[:3]
+        if n == 0:
+            return
+        if self.size is None:
+            self.size = (w, h)
+            self.pieces.append(_gif_header(w, h))
+        elif self.size != (w, h):
+            raise ValueError("frames of %d x %d after frames of %d x %d" % ((w, h) + self.size))
+        ws = ops.gif_workspace(n, h, w, frames.device)
+        indices, palettes, _ = ops.gif_quantize(frames, ws)
+        data, lengths = ops.gif_lzw(indices, h, w, ws)
+        lengths = lengths.cpu().numpy()                                # the one read that decides how much data follows
+        if (lengths < 0).any():
+            raise NerfHipError("gif_lzw: a dictionary probe exceeded its bound in frame %d" % int(np.flatnonzero(lengths < 0)[0]))
+        data = data[:, :int(lengths.max())].cpu().numpy()
+        palettes = palettes.cpu().numpy()
+        head = _gif_frame_header(w, h, self.fps)
+        for i in range(n):
+            self.pieces += [head, palettes[i].tobytes(), b"\x08", data[i, :lengths[i]].tobytes(), b"\x00"]
+        self.n_frames += n
+
+    def getvalue(self):
+        if self.size is None:
+            raise ValueError("a GIF needs at least one frame")
+        return b"".join(self.pieces) + b"\x3b"
+
+
+def gif_bytes(frames, fps=30, batch=GIF_BATCH):
+    """(F, H, W, 3) uint8 frames on the device -> the animated GIF's file contents, `batch` frames per GPU call."""
+    out = GifWriter(fps)
+    for i in range(0, frames.shape[0], batch):
+        out.append(frames[i:i + batch])
+    return out.getvalue()
+
+
+def write_gif(path, frames, fps=30):
+    """imageio.mimsave(path, frames, fps=fps) of eval.py:145 for frames on the device."""
+    data = gif_bytes(frames, fps)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def read_gif(data):
+    """Decoder for GIF files (contents, or a path) of non-interlaced frames: {'width', 'height', 'loop' (None without a
+    NETSCAPE2.0 block), 'palettes': [(n, 3) uint8], 'indices': [(h, w) uint8], 'delays': [centiseconds], 'offsets': [(left,
+    top)]}.  Frames are returned as stored: no compositing, transparency or disposal."""
+    if isinstance(data, str):
+        with open(data, "rb") as f:
+            data = f.read()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    if bytes(buf[:6]) not in (b"GIF87a", b"GIF89a"):
+        raise ValueError("not a GIF file")
+    out = {"width": int(buf[6]) | int(buf[7]) << 8, "height": int(buf[8]) | int(buf[9]) << 8, "loop": None, "palettes": [],
+           "indices": [], "delays": [], "offsets": []}
+    pos = 13
+    global_table = None
+    if buf[10] & 0x80:
+        n = 2 << (int(buf[10]) & 7)
+        global_table = buf[pos:pos + 3 * n].reshape(n, 3).copy()
+        pos += 3 * n
+
+    def sub_blocks(pos):
+        parts = []
+        while buf[pos] != 0:
+            parts.append(buf[pos + 1:pos + 1 + int(buf[pos])])
+            pos += 1 + int(buf[pos])
+        return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), pos + 1
+
+    delay = 0
+    while True:
+        if pos >= len(buf):
+            raise ValueError("GIF without a trailer")
+        kind = int(buf[pos])
+        pos += 1
+        if kind == 0x3b:
+            return out
+        if kind == 0x21:
+            label = int(buf[pos])
+            body, pos = sub_blocks(pos + 1)
+            if label == 0xf9 and len(body) >= 4:
+                delay = int(body[1]) | int(body[2]) << 8
+            elif label == 0xff and len(body) >= 14 and bytes(body[:11]) == b"NETSCAPE2.0" and body[11] == 1:
+                out["loop"] = int(body[12]) | int(body[13]) << 8
+            continue
+        if kind != 0x2c:
+            raise ValueError("unknown GIF block 0x%02x" % kind)
+        left, top, w, h = (int(buf[pos + 2 * k]) | int(buf[pos + 2 * k + 1]) << 8 for k in range(4))
+        flags = int(buf[pos + 8])
+        pos += 9
+        if flags & 0x40:
+            raise ValueError("interlaced GIF frames are not supported")
+        table = global_table
+        if flags & 0x80:
+            n = 2 << (flags & 7)
+            table = buf[pos:pos + 3 * n].reshape(n, 3).copy()
+            pos += 3 * n
+        min_size = int(buf[pos])
+        body, pos = sub_blocks(pos + 1)
+        out["palettes"].append(table)
+        out["indices"].append(_gif_lzw_decode(body, min_size, w * h).reshape(h, w))
+        out["delays"].append(delay)
+        out["offsets"].append((left, top))
+        delay = 0
+
+
+def _gif_lzw_decode(body, min_size, n_pixels):
+    """Variable-width LZW of GIF: codes as (prefix code, last byte, length) arrays, strings written back to front."""
+    if not 2 <= min_size <= 8:
+        raise ValueError("LZW minimum code size %d" % min_size)
+    clear = 1 << min_size
+    prefix = np.zeros(4096, np.int32)
+    last = np.zeros(4096, np.uint8)
+    first = np.zeros(4096, np.uint8)
+    length = np.ones(4096, np.int32)
+    last[:clear] = first[:clear] = np.arange(clear)
+    stream = int.from_bytes(body.tobytes(), "little")
+    n_bits = 8 * len(body)
+    out = np.zeros(n_pixels, np.uint8)
+    at = bit = 0
+    width, free, prev = min_size + 1, clear + 2, -1
+    while True:
+        if bit + width > n_bits:
+            raise ValueError("LZW data ends before its end code")
+        code = (stream >> bit) & ((1 << width) - 1)
+        bit += width
+        if bit > 1 << 16:                     # keep the shifts short
+            stream >>= bit
+            n_bits -= bit
+            bit = 0
+        if code == clear:
+            width, free, prev = min_size + 1, clear + 2, -1
+            continue
+        if code == clear + 1:
+            break
+        if prev < 0:
+            if code >= clear:
+                raise ValueError("LZW: a string code directly after a clear code")
+        else:
+            if code > free or (code == free and free >= 4096):
+                raise ValueError("LZW: code %d is not in the table" % code)
+            if free < 4096:
+                prefix[free], length[free], first[free] = prev, length[prev] + 1, first[prev]
+                last[free] = first[prev] if code == free else first[code]
+                free += 1
+                if free == 1 << width and width < 12:
+                    width += 1
+        n = int(length[code])
+        if at + n > n_pixels:
+            raise ValueError("LZW data holds more pixels than the frame")
+        c = code
+        for k in range(at + n - 1, at - 1, -1):
+            out[k] = last[c]
+            c = prefix[c]
+        at += n
+        prev = code
+    if at != n_pixels:
+        raise ValueError("LZW data holds %d pixels, the frame has %d" % (at, n_pixels))
+    return out

@@ -196,14 +196,19 @@ def image_to_u8(rgb):
 
 
 @torch.no_grad()
-def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="pfm", window_size=3):
-    """The loop of the reference's eval.py (eval.py:112-149, without the gif) with its tail on the GPU.
+def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="pfm", window_size=3, gif_path=None, fps=30):
+    """The loop of the reference's eval.py (eval.py:112-149) with its tail on the GPU.
 
     dataset: `len`, `img_wh` = (w, h), items with 'rays' (h*w, 8) and optionally 'rgbs' (h*w, 3).  renderer: rays on the GPU ->
     a dict with 'rgb_fine' (h*w, 3) and 'depth_fine' (h*w,) (a `GraphRenderer`, or a closure over `batched_inference`).
     Per image: render; PSNR and SSIM against the ground truth on the device; uint8 on the device; copy the bytes to the host;
     with `dir_name`, write `{i:03d}.png` and (save_depth) `depth_{i:03d}.pfm` / `depth_{i:03d}` as `save_image_outputs` does.
     The metric scalars stay on the device and are read once, after the last image.
+    With `gif_path`, the uint8 frames also stay on the device, `imageio_min.GIF_BATCH` (8) at a time: a full batch is quantised
+    and LZW-coded there (`imageio_min.GifWriter`) and its data appended on the host, and the file is written after the loop as
+    `imageio.mimsave(gif_path, imgs, fps=fps)` of eval.py:145 is.  A batch holds per frame 3 bytes per pixel of frames, 1 of
+    indices, about 1.5 of worst-case data and 38.5 KB per 3838 pixels of strip workspace — about 10 MB at 800 x 800, 81 MB per
+    batch.  With `gif_path=None` nothing of this runs: the returned dict and the files written are what they were.
 
     Returns {'psnr': [...], 'ssim': [...], 'mean_psnr', 'mean_ssim', 'images': [(h, w, 3) uint8 arrays]} (the lists are empty
     and the means None for a dataset without ground truth)."""
@@ -212,11 +217,12 @@ def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="p
     import numpy as np
 
     from . import metrics
-    from .imageio_min import depth_bytes, save_pfm, write_png
+    from .imageio_min import GIF_BATCH, GifWriter, depth_bytes, save_pfm, write_png
     w, h = dataset.img_wh
     if dir_name is not None:
         os.makedirs(dir_name, exist_ok=True)
     images, psnrs, ssims = [], [], []
+    gif, pending = (GifWriter(fps), []) if gif_path is not None else (None, None)
     for i in range(len(dataset)):
         sample = dataset[i]
         rays = sample["rays"]
@@ -227,8 +233,14 @@ def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="p
             gt = sample["rgbs"].to(dev).reshape(h * w, 3)
             psnrs.append(metrics.psnr(gt, rgb))                      # eval.py:143's argument order
             ssims.append(metrics.ssim_hw3(rgb, gt, h, w, window_size=window_size))
-        img = image_to_u8(rgb).reshape(h, w, 3).cpu().numpy()
+        img_dev = image_to_u8(rgb).reshape(h, w, 3)
+        img = img_dev.cpu().numpy()
         images.append(img)
+        if gif is not None:
+            pending.append(img_dev)
+            if len(pending) == GIF_BATCH:
+                gif.append(torch.stack(pending))
+                pending = []
         if dir_name is None:
             continue
         if save_depth:
@@ -239,6 +251,11 @@ def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="p
                 with open(os.path.join(dir_name, "depth_%03d" % i), "wb") as f:
                     f.write(depth_bytes(depth))
         write_png(os.path.join(dir_name, "%03d.png" % i), img)
+    if gif is not None and images:
+        if pending:
+            gif.append(torch.stack(pending))
+        with open(gif_path, "wb") as f:
+            f.write(gif.getvalue())
     out = {"psnr": [], "ssim": [], "mean_psnr": None, "mean_ssim": None, "images": images}
     if psnrs:
         both = torch.stack([torch.stack(psnrs), torch.stack(ssims)]).cpu().numpy()       # the one read of the metric scalars

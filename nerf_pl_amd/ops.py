@@ -1098,6 +1098,58 @@ def depth_colormap(depth, table, want_float=True, want_bytes=False):
     return out_f, out_b
 
 
+# ------------------------------------------------------------------------------- animated GIF (eval.py:145)
+GIF_STRIP = 3838            # NERFHIP_GIF_STRIP
+
+
+def gif_workspace(F, H, W, device):
+    """The scratch buffer both GIF calls take (about 38.5 KB per 3838-pixel strip plus 168 KB per frame)."""
+    nbytes = _lib.load().nerfhip_gif_workspace_bytes(F, H, W)
+    if F > 0 and nbytes == 0:
+        raise NerfHipError("gif: %d frames of %d x %d are refused (1..65535 per side, at most 2^26 pixels, at most 65535 frames)"
+                           % (F, H, W))
+    return torch.empty(max(1, nbytes // 8), device=device, dtype=torch.int64)
+
+
+@device_guard
+def gif_quantize(frames, workspace=None):
+    """nerfhip_gif_quantize: frames (F, H, W, 3) uint8 on the device -> (indices (F, H*W) uint8, palettes (F, 256, 3) uint8,
+    box_counts (F,) int32): every frame's own median-cut palette.  No host synchronisation."""
+    frames = _require_u8("gif_quantize: frames", frames)
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise NerfHipError("gif_quantize: expected (F, H, W, 3), got %s" % (tuple(frames.shape),))
+    F, H, W = frames.shape[:3]
+    dev = frames.device
+    lib = _lib.load()
+    ws = workspace if workspace is not None else gif_workspace(F, H, W, dev)
+    indices = torch.empty((F, H * W), device=dev, dtype=torch.uint8)
+    palettes = torch.empty((F, 256, 3), device=dev, dtype=torch.uint8)
+    boxes = torch.empty((F,), device=dev, dtype=torch.int32)
+    check(lib.nerfhip_gif_quantize(ptr(frames), F, H, W, ptr(indices), ptr(palettes), ptr(boxes), ptr(ws), stream_ptr()),
+          "nerfhip_gif_quantize")
+    return indices, palettes, boxes
+
+
+@device_guard
+def gif_lzw(indices, H, W, workspace=None):
+    """nerfhip_gif_lzw: indices (F, H*W) uint8 on the device -> (data (F, stride) uint8, lengths (F,) int32): per frame the
+    sub-blocked LZW image data (strips of GIF_STRIP pixels, each behind a clear code) and its length in bytes; the bytes behind
+    a frame's length are undefined.  No host synchronisation: a length of -1 (a dictionary probe bound was hit) is for the
+    caller to check when it reads the lengths (imageio_min.gif_bytes does)."""
+    indices = _require_u8("gif_lzw: indices", indices)
+    if indices.dim() != 2 or indices.shape[1] != H * W:
+        raise NerfHipError("gif_lzw: expected (F, %d) indices for %d x %d frames, got %s" % (H * W, H, W, tuple(indices.shape)))
+    F = indices.shape[0]
+    dev = indices.device
+    lib = _lib.load()
+    ws = workspace if workspace is not None else gif_workspace(F, H, W, dev)
+    stride = lib.nerfhip_gif_data_stride(H, W)
+    data = torch.empty((F, stride), device=dev, dtype=torch.uint8)
+    lengths = torch.empty((F,), device=dev, dtype=torch.int32)
+    check(lib.nerfhip_gif_lzw(ptr(indices), F, H, W, ptr(data), ptr(lengths), ptr(ws), stream_ptr()), "nerfhip_gif_lzw")
+    return data, lengths
+
+
 # ------------------------------------------------------------------------------- scene loading (datasets/blender.py:47-58, 90-95)
 def _require_u8(name, t):
     if not torch.is_tensor(t):
