@@ -145,7 +145,9 @@ int nerfhip_composite_train(const float* raw, const float* z, const float* rays,
 
 /* The coarse pass of a training step (rendering.py:143-172 + :223-229): nerfhip_composite_train and, for the same ray in the same
  * wave, nerfhip_fine_z_ex on its weights (u / u_stride / N_i / eps / z_fine / row_total as there) — the weights travel from the quadrature to the
- * inverse-CDF sampling through LDS (`weights` may be NULL).  Bit-identical to the two launches.                            */
+ * inverse-CDF sampling through LDS (`weights` may be NULL).  Bit-identical to the two launches.  3 <= S <= 2048 like the other
+ * training entry points: two rays' tables, (7 S + 2 N_i) floats each, share the workgroup's LDS — up to the 160 KB of the CU
+ * (S = 2048 with N_i = 128: 114 KB), where nerfhip_fine_z_ex alone holds four rays in 64 KB and stops at 4 S + 2 N_i <= 4092.  */
 int nerfhip_composite_train_fine_z(const float* raw, const float* z, const float* rays, const float* noise, float noise_std,
                                    int white_back, const float* target, float grad_scale, float* weights, float* rgb, float* depth,
                                    float* opacity, float* g_raw, int64_t B, int S, const float* u, int64_t u_stride, int N_i,

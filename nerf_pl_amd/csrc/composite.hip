@@ -278,11 +278,16 @@ extern "C" int nerfhip_composite_train_fine_z(const float* raw, const float* z, 
     NERFHIP_CHECK_ARG(B >= 0 && S >= 3 && S <= 2048 && N_i >= 1 && (row_total == 0 || row_total == 1));
     const int S4 = (S + 3) & ~3, N4 = (N_i + 3) & ~3;
     const size_t per_wave = (size_t)(2 * S4 + 3 * S4 + N4 + ((S + 1 + 3) & ~3) + N4) * sizeof(float);
-    NERFHIP_CHECK_ARG(2 * per_wave <= 65536);
+    NERFHIP_CHECK_ARG(2 * per_wave <= 160 * 1024);      // the LDS of a gfx950 CU: S = 2048 with N_i = 128 takes 114 KB
     if (B == 0) return 0;
     NERFHIP_CHECK_ARG(raw && z && rays && target && rgb && depth && opacity && g_raw && z_fine);
     if ((((uintptr_t)raw) | ((uintptr_t)g_raw)) & 15) return NERFHIP_E_ALIGN;
     if (noise_std == 0.0f) noise = nullptr;
+    if (2 * per_wave > 65536) {                         // beyond what every launch may ask for (a training step is not: 5 KB)
+        const hipError_t e = hipFuncSetAttribute((const void*)nerfhip::composite_train_fine_z_kernel,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * per_wave));
+        if (e != hipSuccess) return (int)e;
+    }
     hipLaunchKernelGGL(nerfhip::composite_train_fine_z_kernel, dim3((unsigned)((B + 1) / 2)), dim3(256), 2 * per_wave,
                        (hipStream_t)stream, raw, z, rays, noise, noise_std, white_back, target, grad_scale, weights, rgb, depth,
                        opacity, g_raw, B, S, u, u_stride, N_i, eps, z_fine, row_total);
