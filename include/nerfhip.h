@@ -548,6 +548,26 @@ int nerfhip_mesh_color_finish(const double* accum, int64_t V, uint8_t* out, nerf
 /* out (n) uint8 = trunc(float32(rgb * 255)): the vertex-normal mode's colours (extract_color_mesh.py:279)                  */
 int nerfhip_mesh_rgb_to_u8(const float* rgb, int64_t n, uint8_t* out, nerfhip_stream_t stream);
 
+/* ---- Unity volume file  (extract_mesh.ipynb, cell "Generate .vol file for volume rendering in Unity"; nerf_pl_amd/volume.py,
+ * DESIGN.md "Volume export") ------------------------------------------------------------------------------------------------
+ * The notebook's pack, for the points first_index .. first_index+n-1 of a lattice whose full-network output is rgbsigma (n,4)
+ * float32 (16-byte aligned), neg_cell = float32(-(xmax - xmin) / N):
+ *     sigma = np.maximum(rgbsigma[:, -1], 0);  a = 1 - np.exp(-(xmax-xmin)/N*sigma)      t = neg_cell * sigma (one fp32 multiply),
+ *                                                                                        a = 1.0f - (float)exp((double)t)
+ *     i = np.where(a > 0)[0]                                                             kept iff a > 0 (NaN, sigma <= 0: dropped)
+ *     rgb = (rgbsigma[:, :3].numpy()*255).astype(np.uint32)                              one fp32 multiply, truncated, clamped 0..255
+ *     s = rgb.dot([1<<24, 1<<16, 1<<8]) + (a*255).astype(np.uint32)                      R<<24 | G<<16 | B<<8 | A
+ *     res = np.stack([i, s], -1).astype(np.uint32)                                       records (index, s), increasing index
+ * The kept records are appended at records[2 * (*cursor)] onward (records 8-byte aligned, room for `capacity` records) and the
+ * DEVICE int64 *cursor is advanced by the kept count, so a lattice packed in chunks needs no host round trip.  A record that
+ * would land at or beyond `capacity` is not written; the cursor still advances by the full count (overflow shows there).
+ * Three launches (count, one-workgroup scan, emit) on `stream`; nothing is allocated, nothing synchronises.  n == 0 is success
+ * and launches nothing; n < 0, capacity < 0, first_index < 0, first_index + n > 2^32 and null pointers with n > 0 are
+ * NERFHIP_E_BADARG.  workspace: nerfhip_vol_workspace_bytes(n) bytes, 8-byte aligned (0 for n < 0 or n > 2^32).               */
+size_t nerfhip_vol_workspace_bytes(int64_t n);
+int nerfhip_vol_pack(const float* rgbsigma, int64_t n, int64_t first_index, float neg_cell, void* workspace, uint32_t* records,
+                     int64_t capacity, int64_t* cursor, nerfhip_stream_t stream);
+
 /* ---- scene loading  (datasets/blender.py:47-58,90-95; nerf_pl_amd/datasets, DESIGN.md "Scene loading") -----------------------
  * What the reference does per image on the host with PIL and torchvision, on byte images in HBM.  All three: n == 0 is success;
  * null pointers with n > 0, sizes < 0 and unsupported channel counts are NERFHIP_E_BADARG before anything is launched.

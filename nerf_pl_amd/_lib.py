@@ -125,6 +125,8 @@ SIGNATURES = {
     "nerfhip_mesh_color_accumulate": [_c_void_p, _c_void_p, _c_void_p, _i64, _f32, _c_void_p, _c_void_p],
     "nerfhip_mesh_color_finish": [_c_void_p, _i64, _c_void_p, _c_void_p],
     "nerfhip_mesh_rgb_to_u8": [_c_void_p, _i64, _c_void_p, _c_void_p],
+    "nerfhip_vol_workspace_bytes": [_i64],
+    "nerfhip_vol_pack": [_c_void_p, _i64, _i64, _f32, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p],
     "nerfhip_png_unfilter": [_c_void_p, _c_void_p, _c_void_p, _int, _int, _int, _int, _c_void_p],
     "nerfhip_resize_rgba_lanczos": [_c_void_p, _c_void_p, _c_void_p, _int, _int, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p,
                                     _int, _c_void_p, _c_void_p, _c_void_p, _int, _c_void_p],
@@ -189,7 +191,7 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_marching_cubes_workspace_bytes": ctypes.c_size_t, "nerfhip_mesh_cluster_workspace_bytes": ctypes.c_size_t,
              "nerfhip_jpeg_planes_bytes": ctypes.c_size_t, "nerfhip_ssim_workspace_bytes": ctypes.c_size_t,
              "nerfhip_depth_colormap_workspace_bytes": ctypes.c_size_t, "nerfhip_gif_workspace_bytes": ctypes.c_size_t,
-             "nerfhip_gif_data_stride": ctypes.c_size_t}
+             "nerfhip_gif_data_stride": ctypes.c_size_t, "nerfhip_vol_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 
