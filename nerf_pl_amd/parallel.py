@@ -267,8 +267,10 @@ class GradSync:
         # backward wrote them as consecutive slices of one allocation: ONE all-reduce over that range.  Buffers that are not adjacent
         # (a modular-graph step) go over RCCL as ONE grouped launch (ncclGroupStart / End around the per-model all-reduces: same
         # values — each buffer is still its own all-reduce), elsewhere (gloo: the CPU tests) one call each.
+        # (in the order of their storage, not of `self.models`: the backward lays the fine model's buffer first, the system lists the
+        # coarse model first — taken in the models' order the slices never looked consecutive and each went as its own message)
         grouped = None
-        joint = self.joint_of(direct) if len(direct) > 1 else None
+        joint = self.joint_of(sorted(direct, key=lambda f: f.storage_offset())) if len(direct) > 1 else None
         if joint is not None:
             works.append((dist.all_reduce(joint, op=op, group=self.group, async_op=True), joint, None, div))
             direct = []

@@ -465,6 +465,17 @@ def _worker(rank, world, port, n_rays, q):
             gs12.sync()
             ok_joint = ok_joint and calls11["n"] == 1 and calls11["numel"] == [2 * sum(sizes)] and entered["n"] == 0
             ok_joint = ok_joint and all(torch.allclose(f, base3 * want * (k + 1) * 2.0) for k, f in enumerate(flats12))
+            # ... whatever the order the models are listed in: the real backward lays the FINE model's buffer first while NeRFSystem
+            # lists the coarse model first (on the GPU: tests/test_gpu_world2.py) — still ONE message over the joint range
+            ms14, flats14, _ = joint_models(3.0)
+            gs14 = parallel.GradSync(ms14[::-1])
+            gs14.hooks_enabled = False
+            calls11["n"], calls11["numel"] = 0, []
+            for mm, fl in zip(ms14, flats14):
+                adopt(mm, fl)
+            gs14.sync()
+            ok_joint = ok_joint and calls11["numel"] == [2 * sum(sizes)]
+            ok_joint = ok_joint and all(torch.allclose(f, base3 * want * (k + 1) * 3.0) for k, f in enumerate(flats14))
             # gradient accumulation under the joint hook: nothing is issued early, sync() averages the accumulated p.grad
             ms13, flats13, _ = joint_models(1.0)
             gs13 = parallel.GradSync(ms13)
