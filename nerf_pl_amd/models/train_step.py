@@ -153,35 +153,34 @@ class _TrainRender(torch.autograd.Function):
             m.check_pack_serial(serial)
         hooked = any(getattr(m, "_grad_ready_hook", None) is not None for m in models)
         joint_hook = getattr(models[0], "_grads_ready_hook", None) if hooked else None
-        if hooked and joint_hook is not None and all(getattr(m, "_grads_ready_hook", None) == joint_hook for m in models):
-            # N > 1 ranks, the default form (parallel.GradSync(form="merged")): the SAME launches as the one-rank step — one chain,
-            # one dW, one reduce launch for both models — and then ONE all-reduce over the step's gradients, which the launch wrote as
-            # consecutive slices of one buffer.  (Measured at world 1: the per-model form below costs 7.6 % of the step before any
-            # wire time — two dW launches fill the chip worse than one; a single 4.77 MB all-reduce exposes less than that.)
-            grads = ops.mlp_bwd_multi(entries, dtype, g_scale=g_scale)
-            for m, g in zip(models, grads):
-                m._flat_grad = g[2]
-            joint_hook(models, [g[2] for g in grads])
-        elif hooked:
-            # N > 1 ranks, form="per_model": per model chain -> dW -> reduce -> grad-ready hook, so that the fine model's all-reduce
-            # travels while the coarse model's backward still runs (parallel.GradSync)
-            grads = []
-            for m, entry in zip(models, entries):
-                ((gw, gb, flat),) = ops.mlp_bwd_multi([entry], dtype, g_scale=g_scale)
-                m._flat_grad = flat
-                m._grad_ready_hook(m, flat)
-                grads.append((gw, gb, flat))
-        else:
+        merged = joint_hook is not None and all(getattr(m, "_grads_ready_hook", None) == joint_hook for m in models)
+        adam = None
+        if not hooked:
             # Adam inside the reduce kernel only when these gradients ARE the step's gradients: with gradients already accumulated
             # in p.grad (a second backward before the optimizer step) the update would be applied once per backward
             if ctx.adam is not None and any(p.grad is not None for m in models for p in m.flat_params()):
                 ctx.adam = None
             adam = ctx.adam.handle(models) if ctx.adam is not None else None
-            grads = ops.mlp_bwd_multi(entries, dtype, adam=adam, g_scale=g_scale)
-            for m, g in zip(models, grads):
+        # The launch groups.  One rank, and N > 1 ranks in the default form (parallel.GradSync(form="merged")): ONE group — one chain,
+        # one dW, one reduce launch for both models — and under the hook ONE all-reduce over the step's gradients, which the launch
+        # wrote as consecutive slices of one buffer.  form="per_model": per model chain -> dW -> reduce -> grad-ready hook, fine
+        # first, so that the fine model's all-reduce travels while the coarse model's backward still runs.  (Measured at world 1:
+        # the per-model form costs 7.6 % of the step before any wire time — two dW launches fill the chip worse than one; a single
+        # 4.77 MB all-reduce exposes less than that.)
+        groups = [[k] for k in range(n_models)] if hooked and not merged else [list(range(n_models))]
+        grads = []
+        for group in groups:
+            ms = [models[k] for k in group]
+            got = ops.mlp_bwd_multi([entries[k] for k in group], dtype, adam=adam, g_scale=g_scale)
+            for m, g in zip(ms, got):
                 m._flat_grad = g[2]
-            if ctx.adam is not None:
-                ctx.adam.applied_in_backward(models)
+            if merged:
+                joint_hook(ms, [g[2] for g in got])
+            elif hooked:
+                ms[0]._grad_ready_hook(ms[0], got[0][2])
+            grads += got
+        if adam is not None:
+            ctx.adam.applied_in_backward(models)
         ctx.entries = None
         by_model = {id(m): g for m, g in zip(models, grads)}
         out = []

@@ -13,7 +13,8 @@ over xGMI on ROCm; "gloo" in the CPU tests).
   coarse model's backward is still running (autograd runs the fine model first; `GradSync._on_grad_ready`) — what DDP's
   bucket hooks give the reference, at the price of un-merging the launches (7.6 % of the step at world 1).
 """
-import os
+import contextlib
+import warnings
 
 import torch
 import torch.distributed as dist
@@ -61,14 +62,16 @@ def render_sharded(render_fn, rays, keys=("rgb_fine", "depth_fine", "opacity_fin
     return out
 
 
-_COALESCE = os.environ.get("NERFHIP_COALESCE_ALLREDUCE", "1") != "0"      # (A/B switch)
+class _InFlight:
+    """One all-reduce a backward hook issued and sync() has not settled yet."""
+    __slots__ = ("work", "buffer", "needs_division", "owners", "done")
 
-
-class _Done:
-    """A finished piece of work (its collective was waited for as part of a group)."""
-
-    def wait(self):
-        return True
+    def __init__(self, work, buffer, needs_division, owners):
+        self.work = work                        # the async handle
+        self.buffer = buffer                    # the tensor the all-reduce rewrites: one model's flat buffer, or the joint range
+        self.needs_division = needs_division
+        self.owners = owners                    # [(model, flat)]: one pair per model whose gradients `buffer` holds
+        self.done = False                       # waited for and divided: `buffer` holds the rank average
 
 
 class GradSync:
@@ -87,18 +90,18 @@ class GradSync:
         self.group = group
         self.force = force          # run the collectives even at world size 1 (tests the RCCL path on one GPU)
         self.overlap = overlap
-        # form of the fused step's backward under this sync: "merged" = the one-rank launches + ONE all-reduce of the step's joint
-        # gradient buffer; "per_model" = per model chain -> dW -> reduce -> all-reduce (the fine model's travels under the coarse
-        # model's backward).  NERFHIP_GRAD_SYNC_FORM overrides the default for A/B runs (tools/launch_scale.sh measures both).
-        self.form = form if form is not None else os.environ.get("NERFHIP_GRAD_SYNC_FORM", "merged")
+        # form of the fused step's backward under this sync: "merged" (also None) = the one-rank launches + ONE all-reduce of the
+        # step's joint gradient buffer; "per_model" = per model chain -> dW -> reduce -> all-reduce (the fine model's travels under
+        # the coarse model's backward; tools/launch_scale.sh measures both).
+        self.form = form if form is not None else "merged"
         if self.form not in ("merged", "per_model"):
             raise ValueError("GradSync form must be 'merged' or 'per_model', got %r" % (self.form,))
         self.issue_log = []         # ("model", id(model)) / ("joint", n_models) per hook-issued collective since the last sync() (tests)
         self.hooks_enabled = True   # GraphedTrainStep switches the hooks off while it captures/replays a graph that
                                     # must not contain the collective (two-graph mode)
-        self._inflight = {}         # id(model) -> [(work, flat, needs_division)] issued from the hook since the last sync()
+        self._inflight = []         # the _InFlight records of the all-reduces issued from the hooks since the last sync()
         self.started_early = 0      # statistics: all-reduces issued from the hook (tests assert on it)
-        self._coalesce = _COALESCE  # the per-model all-reduces of sync() as one grouped RCCL launch
+        self._coalesce = True       # the per-model all-reduces of sync() as one grouped RCCL launch
         self._coalesce_backends = ("nccl",)     # (the gloo CPU test adds "gloo" to drive the same branch)
         if overlap:
             self.attach()
@@ -136,24 +139,6 @@ class GradSync:
             return dist.ReduceOp.AVG, False
         return dist.ReduceOp.SUM, True
 
-    def _on_grad_ready(self, model, flat):
-        """Called by the fused backward when `flat` (the model's 24 gradients) is complete, BEFORE autograd hands the views
-        to the parameters.  The all-reduce is started here only when autograd is going to adopt the views as `p.grad`
-        (every `p.grad` is None: zero_grad(set_to_none=True), no accumulation): otherwise autograd would accumulate the views
-        into existing `.grad` tensors on the compute stream while the collective rewrites `flat` on the communicator's."""
-        if not (self.hooks_enabled and self.overlap and self.active()):
-            return
-        # a second backward before sync(): its accumulation into p.grad (views of the first buffer) must be ordered after
-        # the collective that is still rewriting that buffer — finish (wait, divide) what is in flight for this model
-        self._finish(self._inflight.get(id(model), ()))
-        if any(p.grad is not None for p in model.parameters()):
-            return                                     # gradient accumulation: sync() reduces the accumulated p.grad
-        op, div = self._avg_op()
-        work = dist.all_reduce(flat, op=op, group=self.group, async_op=True)
-        self._inflight.setdefault(id(model), []).append([work, flat, div, False])
-        self.started_early += 1
-        self.issue_log.append(("model", id(model)))
-
     @staticmethod
     def joint_of(flats):
         """The ONE tensor whose consecutive slices `flats` are (ops.mlp_bwd_multi allocates a step's flat gradient buffers that
@@ -169,36 +154,51 @@ class GradSync:
         lo = flats[0].storage_offset() - base.storage_offset()
         return base.reshape(-1)[lo:lo + sum(f.numel() for f in flats)]
 
-    def _on_grads_ready(self, models, flats):
-        """form="merged": called ONCE by the fused backward when the flat gradient buffers of ALL its models are complete (one
-        reduce launch wrote them), BEFORE autograd hands the views to the parameters.  Issues ONE all-reduce over the joint buffer,
-        asynchronously on the communicator's stream; the same adoption rule as `_on_grad_ready`."""
+    # -- the backward's hooks ---------------------------------------------------------------------------------------
+    def _on_grad_ready(self, model, flat):
+        """form="per_model" (and the modular backward): called when `flat` (the model's 24 gradients) is complete.  The one-model
+        case of `_on_grads_ready`, always that model's own all-reduce."""
+        self._on_grads_ready([model], [flat], joint=False)
+
+    def _on_grads_ready(self, models, flats, joint=True):
+        """Called by the fused backward when the flat gradient buffers `flats` of `models` are complete (form="merged": ONCE, for
+        ALL its models — one reduce launch wrote them), BEFORE autograd hands the views to the parameters.  Issues ONE all-reduce
+        over the joint buffer (`joint`), else one per model, asynchronously on the communicator's stream.  The all-reduce is started
+        here only when autograd is going to adopt the views as `p.grad` (every `p.grad` is None: zero_grad(set_to_none=True), no
+        accumulation): otherwise autograd would accumulate the views into existing `.grad` tensors on the compute stream while the
+        collective rewrites the buffer on the communicator's."""
         if not (self.hooks_enabled and self.overlap and self.active()):
             return
-        for m in models:
-            self._finish(self._inflight.get(id(m), ()))
-        self._finish(self._inflight.get("joint", ()))
+        # a second backward before sync(): its accumulation into p.grad (views of the first buffer) must be ordered after
+        # the collective that is still rewriting that buffer — finish (wait, divide) what is in flight for these models
+        self._finish(r for r in self._inflight if any(m is o for o, _ in r.owners for m in models))
         if any(p.grad is not None for m in models for p in m.parameters()):
             return                                     # gradient accumulation: sync() reduces the accumulated p.grad
-        joint = self.joint_of(flats)
-        if joint is None:                              # not one allocation (an older caller): one collective per model
-            for m, f in zip(models, flats):
-                self._on_grad_ready(m, f)
-            return
+        whole = self.joint_of(flats) if joint else None
         op, div = self._avg_op()
-        work = dist.all_reduce(joint, op=op, group=self.group, async_op=True)
-        self._inflight.setdefault("joint", []).append([work, joint, div, False, [id(m) for m in models], list(flats)])
-        self.started_early += 1
-        self.issue_log.append(("joint", len(models)))
+        if whole is not None:
+            sends = [(whole, list(zip(models, flats)))]
+            self.issue_log.append(("joint", len(models)))
+        else:                                          # per model, or not one allocation (an older caller): one collective per model
+            sends = [(f, [(m, f)]) for m, f in zip(models, flats)]
+            self.issue_log.extend(("model", id(m)) for m in models)
+        for buf, owners in sends:
+            work = dist.all_reduce(buf, op=op, group=self.group, async_op=True)
+            self._inflight.append(_InFlight(work, buf, div, owners))
+            self.started_early += 1
 
-    def _finish(self, entries):
+    def _finish(self, records):
         """wait for hook-issued collectives and apply their division: afterwards each buffer holds the rank average"""
-        for e in entries:
-            if not e[3]:
-                e[0].wait()
-                if e[2]:
-                    e[1].div_(dist.get_world_size(self.group))
-                e[3] = True
+        for r in records:
+            if not r.done:
+                r.work.wait()
+                if r.needs_division:
+                    r.buffer.div_(dist.get_world_size(self.group))
+                r.done = True
+
+    def reset(self):
+        """Drop the hook-issued collectives WITHOUT waiting for them: an aborted graph capture recorded them, nothing launched."""
+        self._inflight.clear()
 
     @staticmethod
     def _aliases(params, flat):
@@ -208,109 +208,100 @@ class GradSync:
 
     # -- the step-level call ----------------------------------------------------------------------------------------
     def sync(self):
+        """Leave the rank average in every model's p.grad.  A wait is (work or None, buffer, needs_division, params to copy the
+        buffer back into or None)."""
         if not self.active():
-            self._inflight.clear()
+            self.reset()
             return
-        world = dist.get_world_size(self.group)
-        op, div = self._avg_op()
-        works, direct = [], []
         del self.issue_log[:-64]                        # (a diagnostic: keep the tail)
-        covered = set()
-        early_joint = self._inflight.pop("joint", [])
-        if len(early_joint) == 1 and not early_joint[0][3]:
-            work, joint, jdiv, _, mids, flats = early_joint[0]
-            by_id = {id(m): m for m in self.models}
-            ok = all(i in by_id for i in mids)
-            for i, f in zip(mids, flats):
-                ps = [p for p in by_id[i].parameters() if p.grad is not None] if ok else []
-                ok = ok and bool(ps) and getattr(by_id[i], "_flat_grad", None) is f and self._aliases(ps, f) and not self._inflight.get(i)
-            if ok:
-                works.append((work, joint, None, jdiv))                     # the hook-issued collective IS the step's gradient
-                covered.update(mids)
-        if not covered:
-            # a joint collective whose buffers are not simply p.grad any more (a later backward accumulated on top): finish it,
-            # then reduce p.grad below — exact, as for the per-model case
-            self._finish(early_joint)
-            for e in early_joint:
-                for i, f in zip(e[4], e[5]):
-                    ps = [p for m in self.models if id(m) == i for p in m.parameters() if p.grad is not None]
-                    if ps and not self._aliases(ps, f):
-                        raise RuntimeError("GradSync: the gradient buffer all-reduced from the grads-ready hook was not adopted as "
-                                           "p.grad (autograd copied it while the collective was in flight); construct "
-                                           "GradSync(overlap=False) for this training loop")
+        op, div = self._avg_op()
+        waits, covered, issued_early = self._settle_hook_issued()
+        direct = []
         for m in self.models:
             if id(m) in covered:
                 continue
             flat = getattr(m, "_flat_grad", None)
-            early = self._inflight.pop(id(m), [])
             params = [p for p in m.parameters() if p.grad is not None]
-            if (len(early) == 1 and not early[0][3] and flat is not None and early[0][1] is flat and params
-                    and self._aliases(params, flat)):
-                works.append((early[0][0], flat, None, early[0][2]))        # the overlapped collective IS the gradient
-                continue
-            # early collectives whose buffer is not simply p.grad: finish them, then reduce p.grad.  If p.grad still views
-            # that buffer (a later backward accumulated on top of the averaged values) averaging again is exact — the
-            # averaged part is identical on every rank; if autograd COPIED the views instead of adopting them, the copy
-            # raced with the collective and p.grad is undefined: refuse.
-            self._finish(early)
-            for _, eflat, _, _ in early:
-                if params and not self._aliases(params, eflat):
-                    raise RuntimeError("GradSync: the gradient buffer all-reduced from the grad-ready hook was not adopted as "
-                                       "p.grad (autograd copied it while the collective was in flight); construct "
-                                       "GradSync(overlap=False) for this training loop")
-            if flat is not None and params and self._aliases(params, flat) and not early:
+            if flat is not None and params and self._aliases(params, flat) and id(m) not in issued_early:
                 direct.append(flat)                                      # issued below, together
             elif params:
                 buf = torch.cat([p.grad.reshape(-1) for p in params])
-                works.append((dist.all_reduce(buf, op=op, group=self.group, async_op=True), buf, params, div))
-        # The flat buffers that are reduced as they are (the two-graph step: nothing was started from the hooks).  The fused step's
-        # backward wrote them as consecutive slices of one allocation: ONE all-reduce over that range.  Buffers that are not adjacent
-        # (a modular-graph step) go over RCCL as ONE grouped launch (ncclGroupStart / End around the per-model all-reduces: same
-        # values — each buffer is still its own all-reduce), elsewhere (gloo: the CPU tests) one call each.
+                waits.append((dist.all_reduce(buf, op=op, group=self.group, async_op=True), buf, div, params))
+        waits += self._send_direct(direct, op, div)
+        world = dist.get_world_size(self.group)
+        for work, buf, needs_division, params in waits:
+            if work is not None:
+                work.wait()
+            if needs_division:
+                buf.div_(world)
+            off = 0
+            for p in params or ():
+                n = p.grad.numel()
+                p.grad.copy_(buf[off:off + n].view_as(p.grad))
+                off += n
+
+    def _is_step_gradient(self, rec, records):
+        """The hook-issued collective IS the step's gradient: still running, and each of its buffers is exactly what autograd
+        adopted as p.grad of a model of ours that nothing else was issued for."""
+        if rec.done or any(m is o for r in records if r is not rec for o, _ in r.owners for m, _ in rec.owners):
+            return False
+        for m, flat in rec.owners:
+            params = [p for p in m.parameters() if p.grad is not None]
+            if not (any(m is x for x in self.models) and params and getattr(m, "_flat_grad", None) is flat
+                    and self._aliases(params, flat)):
+                return False
+        return True
+
+    def _settle_hook_issued(self):
+        """-> (waits for the collectives that are the step's gradient, ids of the models those cover, ids of the models named by
+        the others).  The others' buffers are not simply p.grad (a later backward accumulated on top): finish them and let sync()
+        reduce p.grad.  If p.grad still views that buffer, averaging again is exact — the averaged part is identical on every
+        rank; if autograd COPIED the views instead of adopting them, the copy raced with the collective and p.grad is undefined:
+        refuse."""
+        records, self._inflight = self._inflight, []
+        mine = [r for r in records if self._is_step_gradient(r, records)]
+        rest = [r for r in records if not any(r is x for x in mine)]
+        self._finish(rest)
+        for m, flat in (o for r in rest for o in r.owners):
+            params = [p for x in self.models if x is m for p in m.parameters() if p.grad is not None]
+            if params and not self._aliases(params, flat):
+                raise RuntimeError("GradSync: the gradient buffer all-reduced from the backward's hook was not adopted as "
+                                   "p.grad (autograd copied it while the collective was in flight); construct "
+                                   "GradSync(overlap=False) for this training loop")
+        waits = [(r.work, r.buffer, r.needs_division, None) for r in mine]
+        covered = {id(m) for r in mine for m, _ in r.owners}
+        issued_early = {id(m) for r in rest for m, _ in r.owners}
+        return waits, covered, issued_early
+
+    def _send_direct(self, direct, op, div):
+        """The flat buffers that are reduced as they are (the two-graph step: nothing was started from the hooks) -> waits.  The
+        fused step's backward wrote them as consecutive slices of one allocation: ONE all-reduce over that range.  Buffers that
+        are not adjacent (a modular-graph step) go over RCCL as ONE grouped launch (ncclGroupStart / End around the per-model
+        all-reduces: same values — each buffer is still its own all-reduce), elsewhere (gloo: the CPU tests) one call each."""
         # (in the order of their storage, not of `self.models`: the backward lays the fine model's buffer first, the system lists the
         # coarse model first — taken in the models' order the slices never looked consecutive and each went as its own message)
-        grouped = None
         joint = self.joint_of(sorted(direct, key=lambda f: f.storage_offset())) if len(direct) > 1 else None
         if joint is not None:
-            works.append((dist.all_reduce(joint, op=op, group=self.group, async_op=True), joint, None, div))
-            direct = []
+            return [(dist.all_reduce(joint, op=op, group=self.group, async_op=True), joint, div, None)]
         if (len(direct) > 1 and self._coalesce and dist.get_backend(self.group) in self._coalesce_backends
                 and hasattr(dist, "_coalescing_manager")):
-            # Only a stack WITHOUT the grouped form is a reason to fall back, and only before anything can have launched: the manager
-            # launches on __exit__, so an error from inside the block or from the exit (a communicator error, a partial enqueue) is
-            # re-raised — re-issuing after it would double or mismatch collectives across the ranks.
+            grouped = self._send_grouped(direct, op)
+            if grouped is not None:                     # one handle for the launch, then each buffer's division
+                return [(grouped, direct[0], False, None)] + [(None, flat, div, None) for flat in direct]
+        return [(dist.all_reduce(flat, op=op, group=self.group, async_op=True), flat, div, None) for flat in direct]
+
+    def _send_grouped(self, direct, op):
+        """-> the handle of ONE grouped launch of the all-reduces of `direct`, or None where the stack has no grouped form."""
+        # Only a stack WITHOUT the grouped form is a reason to fall back, and only before anything can have launched: the manager
+        # launches on exit, so an error from inside the block or from the exit (a communicator error, a partial enqueue) propagates —
+        # re-issuing after it would double or mismatch collectives across the ranks.
+        with contextlib.ExitStack() as stack:
             try:
-                cm = dist._coalescing_manager(group=self.group, async_ops=True)
-                grouped = cm.__enter__()
+                grouped = stack.enter_context(dist._coalescing_manager(group=self.group, async_ops=True))
             except (AttributeError, TypeError, NotImplementedError) as e:
-                import warnings
                 warnings.warn("GradSync: grouped all-reduce unavailable on this stack (%r); one call per model from now on" % (e,))
                 self._coalesce = False
-                cm = grouped = None
-            if cm is not None:
-                try:
-                    for flat in direct:
-                        dist.all_reduce(flat, op=op, group=self.group)
-                except BaseException as e:
-                    cm.__exit__(type(e), e, e.__traceback__)
-                    raise
-                cm.__exit__(None, None, None)
-        if grouped is not None:
-            works.append((grouped, direct[0], None, False))
-            if div:
-                for flat in direct:
-                    works.append((_Done(), flat, None, True))
-        else:
+                return None
             for flat in direct:
-                works.append((dist.all_reduce(flat, op=op, group=self.group, async_op=True), flat, None, div))
-        self._inflight.clear()
-        for w, buf, params, need_div in works:
-            w.wait()
-            if need_div:
-                buf.div_(world)
-            if params is not None:
-                off = 0
-                for p in params:
-                    n = p.grad.numel()
-                    p.grad.copy_(buf[off:off + n].view_as(p.grad))
-                    off += n
+                dist.all_reduce(flat, op=op, group=self.group)
+        return grouped

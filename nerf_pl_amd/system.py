@@ -340,7 +340,8 @@ class GraphedTrainStep:
                 self.capture_fallback = repr(err) if err is not None else "another rank's capture failed"
                 self.sync_in_graph = False
                 self.graph = None
-                getattr(self.grad_sync, "_inflight", {}).clear()
+                if hasattr(self.grad_sync, "reset"):
+                    self.grad_sync.reset()      # the aborted capture's hook-issued collectives never launched
                 self._arm_draws()           # the aborted capture recorded draw increments that will not be replayed
         if self._two_graphs():
             # two graphs with the collectives issued eagerly in between: the hooks must stay silent, or the fine

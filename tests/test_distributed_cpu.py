@@ -2,8 +2,10 @@
 `parallel.render_sharded` and the gradient averaging of `parallel.GradSync` (both the flat-buffer
 branch the HIP backward produces and the generic branch) — the host logic that `bench.py --gpus N`
 and the 8-GPU configs use with backend nccl (= RCCL).  No HIP compute is called here."""
+import contextlib
 import os
 import socket
+import warnings
 
 import pytest
 import torch
@@ -77,7 +79,80 @@ class _TinySystem(torch.nn.Module):
         return {"loss": ((y - batch["y"]) ** 2).mean()}
 
 
-def _graphed_step_host_logic(rank, world):
+class _Checks:
+    """Every condition a rank checks, by name; none short-circuits another (the parent test prints the names that failed)."""
+
+    def __init__(self):
+        self.results = {}
+
+    def __call__(self, name, cond):
+        assert name not in self.results, name
+        self.results[name] = bool(cond)
+
+
+_SIZES = [p.numel() for p in _Tiny().parameters()]
+_N = sum(_SIZES)
+
+
+def _base():
+    return torch.arange(_N, dtype=torch.float32)
+
+
+def _adopt(model, flat):
+    """what autograd does with the views the backward returns: they become p.grad"""
+    off = 0
+    for p, sz in zip(model.parameters(), _SIZES):
+        p.grad = flat[off:off + sz].view_as(p)
+        off += sz
+
+
+def _accumulate(model, flat):
+    """what autograd does with them when p.grad exists"""
+    off = 0
+    for p, sz in zip(model.parameters(), _SIZES):
+        p.grad += flat[off:off + sz].view_as(p)
+        off += sz
+
+
+def _grads(model):
+    return torch.cat([p.grad.reshape(-1) for p in model.parameters()])
+
+
+def _clear(model):
+    for p in model.parameters():
+        p.grad = None
+
+
+@contextlib.contextmanager
+def _patched(name, make):
+    """dist.<name> replaced by make(real) inside the block; yields the list of the calls' first arguments"""
+    real, seen = getattr(dist, name), []
+    setattr(dist, name, make(real, seen))
+    try:
+        yield seen
+    finally:
+        setattr(dist, name, real)
+
+
+def _counting(real, seen):
+    def f(*a, **kw):
+        seen.append(a[0] if a else None)
+        return real(*a, **kw)
+    return f
+
+
+def _raising(exc):
+    def make(real, seen):
+        def f(*a, **kw):
+            raise exc
+        return f
+    return make
+
+
+def _graphed_step_host_logic(check, rank, world):
+    """The N>1 training step's host logic (system.GraphedTrainStep): eager warm-up steps, capture of [forward+backward] and
+    [optimizer] as two graphs with the collective issued eagerly in between, replays, re-capture on a learning-rate change —
+    with a recording stand-in for the hipGraph backend."""
     from nerf_pl_amd.system import GraphedTrainStep
     g = torch.Generator().manual_seed(100 + rank)           # every rank draws its own batch (weak scaling)
     batches = [{"x": torch.randn(16, 5, generator=g), "y": torch.randn(16, 3, generator=g)} for _ in range(7)]
@@ -88,19 +163,19 @@ def _graphed_step_host_logic(rank, world):
     stepper = GraphedTrainStep(sysm, opt, grad_sync=sync, warmup=2, backend=be, sync_in_graph=False)    # the two-graph form
     for b in batches[:5]:
         stepper(b)
-    ok = be.captures == 2 and stepper.graph is not None and stepper.graph_opt is not None      # two graphs
-    ok = ok and stepper.graph.replays == 3 and stepper.graph_opt.replays == 3                    # calls 3,4,5 replayed
-    ok = ok and sync.hooks_enabled
+    check("step/two_graphs_captured", be.captures == 2 and stepper.graph is not None and stepper.graph_opt is not None)
+    check("step/two_graphs_replayed", stepper.graph.replays == 3 and stepper.graph_opt.replays == 3)     # calls 3,4,5 replayed
+    check("step/hooks_back_on_after_capture", sync.hooks_enabled)
     for grp in opt.param_groups:                            # scheduler step: lr is a captured argument
         grp["lr"] = 0.05
     for b in batches[5:]:
         stepper(b)
-    ok = ok and be.captures == 4 and stepper.captured_lr == 0.05
+    check("step/recaptured_on_lr_change", be.captures == 4 and stepper.captured_lr == 0.05)
     # replicas stay identical (same init, averaged gradients) and equal a single-process run on the averaged gradient
     flat = torch.cat([p.detach().reshape(-1) for p in sysm.parameters()])
     gathered = [torch.empty_like(flat) for _ in range(world)]
     dist.all_gather(gathered, flat)
-    ok = ok and all(torch.equal(gathered[0], t) for t in gathered)
+    check("step/replicas_identical", all(torch.equal(gathered[0], t) for t in gathered))
     ref = _TinySystem()
     ropt = torch.optim.SGD(ref.parameters(), lr=0.1)
     gens = [torch.Generator().manual_seed(100 + r) for r in range(world)]
@@ -114,22 +189,26 @@ def _graphed_step_host_logic(rank, world):
             (ref.training_step(allb[r][i], i)["loss"] / world).backward()
         ropt.step()
     rflat = torch.cat([p.detach().reshape(-1) for p in ref.parameters()])
-    ok = bool(ok and torch.allclose(flat, rflat, rtol=1e-5, atol=1e-6))
+    check("step/two_graphs_follow_reference", torch.allclose(flat, rflat, rtol=1e-5, atol=1e-6))
     # the default IS the one-graph form (round 6; the two-graph form is the agreed fallback and an explicit choice)
-    ok = ok and not GraphedTrainStep(sysm, opt, grad_sync=sync, backend=_RecordingBackend())._two_graphs()
+    check("step/default_is_one_graph", not GraphedTrainStep(sysm, opt, grad_sync=sync, backend=_RecordingBackend())._two_graphs())
+
+    def run(step, optimizer):
+        for i, b in enumerate(batches):
+            if i == 5:
+                for grp in optimizer.param_groups:
+                    grp["lr"] = 0.05
+            step(b)
+
     # the default N > 1 form: ONE graph with the collectives inside (issued by sync() during the captured step) — same replicas
     sys1 = _TinySystem()
     opt1 = torch.optim.SGD(sys1.parameters(), lr=0.1)
     be1 = _RecordingBackend()
     step1 = GraphedTrainStep(sys1, opt1, grad_sync=parallel.GradSync(sys1.models), warmup=2, backend=be1)
-    for i, b in enumerate(batches):
-        if i == 5:
-            for grp in opt1.param_groups:
-                grp["lr"] = 0.05
-        step1(b)
+    run(step1, opt1)
     flat1 = torch.cat([p.detach().reshape(-1) for p in sys1.parameters()])
-    ok = ok and be1.captures == 2 and step1.graph_opt is None and step1.graph.replays == 2        # one graph per capture
-    ok = bool(ok and torch.allclose(flat1, rflat, rtol=1e-5, atol=1e-6))
+    check("step/one_graph_per_capture", be1.captures == 2 and step1.graph_opt is None and step1.graph.replays == 2)
+    check("step/one_graph_follows_reference", torch.allclose(flat1, rflat, rtol=1e-5, atol=1e-6))
     # a stack that cannot capture the collective: the one-graph capture raises, the stepper falls back to two graphs on every
     # rank alike and the replicas still follow the reference run
     sys2 = _TinySystem()
@@ -143,17 +222,13 @@ def _graphed_step_host_logic(rank, world):
 
     be2 = _NoCollectiveInGraph()
     step2 = GraphedTrainStep(sys2, opt2, grad_sync=parallel.GradSync(sys2.models), warmup=2, backend=be2, sync_in_graph=True)
-    import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        for i, b in enumerate(batches):
-            if i == 5:
-                for grp in opt2.param_groups:
-                    grp["lr"] = 0.05
-            step2(b)
+        run(step2, opt2)
     flat2 = torch.cat([p.detach().reshape(-1) for p in sys2.parameters()])
-    ok = ok and step2.capture_fallback is not None and step2._two_graphs() and step2.graph_opt is not None
-    ok = bool(ok and torch.allclose(flat2, rflat, rtol=1e-5, atol=1e-6))
+    check("step/uncapturable_falls_back_to_two_graphs",
+          step2.capture_fallback is not None and step2._two_graphs() and step2.graph_opt is not None)
+    check("step/uncapturable_follows_reference", torch.allclose(flat2, rflat, rtol=1e-5, atol=1e-6))
     # ... and a capture that fails on ONE rank only (rank 1), with its peer waiting in the collective the ranks use to agree on the
     # branch (GradSync.agree_any): BOTH ranks must fall back — a rank replaying a captured all-reduce against a rank issuing an
     # eager one would deadlock — and the replicas still follow the reference run
@@ -169,18 +244,14 @@ def _graphed_step_host_logic(rank, world):
     step3 = GraphedTrainStep(sys3, opt3, grad_sync=parallel.GradSync(sys3.models), warmup=2, backend=_Rank1CannotCapture(), sync_in_graph=True)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        for i, b in enumerate(batches):
-            if i == 5:
-                for grp in opt3.param_groups:
-                    grp["lr"] = 0.05
-            step3(b)
+        run(step3, opt3)
     flat3 = torch.cat([p.detach().reshape(-1) for p in sys3.parameters()])
-    ok = ok and step3.capture_fallback is not None and step3._two_graphs() and step3.graph_opt is not None
-    ok = ok and (("another rank" in step3.capture_fallback) == (rank != 1))
-    return bool(ok and torch.allclose(flat3, rflat, rtol=1e-5, atol=1e-6))
+    check("step/one_rank_fails_both_fall_back", step3.capture_fallback is not None and step3._two_graphs() and step3.graph_opt is not None)
+    check("step/one_rank_fails_peer_is_told", ("another rank" in step3.capture_fallback) == (rank != 1))
+    check("step/one_rank_fails_follows_reference", torch.allclose(flat3, rflat, rtol=1e-5, atol=1e-6))
 
 
-def _fused_backward_issue_order(rank, world):
+def _fused_backward_issue_order(check, rank, world):
     """The fused training node's backward (models/train_step._TrainRender.backward) under the two GradSync forms, with the HIP
     launch (ops.mlp_bwd_multi) replaced by a recorder: WHAT is launched and WHEN the collectives are issued relative to it.
       form="per_model": fine chain/dW/reduce -> the fine model's all-reduce is ISSUED -> only then the coarse model's launches;
@@ -190,7 +261,6 @@ def _fused_backward_issue_order(rank, world):
     from nerf_pl_amd import ops
     from nerf_pl_amd.models import NeRF
     from nerf_pl_amd.models import train_step as TS
-    ok = True
     real_multi, real_ar = ops.mlp_bwd_multi, dist.all_reduce
     for form in ("per_model", "merged"):
         torch.manual_seed(3)
@@ -225,285 +295,270 @@ def _fused_backward_issue_order(rank, world):
             ops.mlp_bwd_multi, dist.all_reduce = real_multi, real_ar
         n = ops.FLAT_GRAD_FLOATS
         if form == "per_model":
-            ok = ok and issued == [("launch", ("fine",)), ("all_reduce", n), ("launch", ("coarse",)), ("all_reduce", n)]
-            ok = ok and gs.issue_log[:2] == [("model", id(fine)), ("model", id(coarse))]
+            check("fused_backward/per_model/launch_and_collective_order",
+                  issued == [("launch", ("fine",)), ("all_reduce", n), ("launch", ("coarse",)), ("all_reduce", n)])
+            check("fused_backward/per_model/issue_log", gs.issue_log[:2] == [("model", id(fine)), ("model", id(coarse))])
         else:
-            ok = ok and issued == [("launch", ("fine", "coarse")), ("all_reduce", 2 * n)] and gs.issue_log[:1] == [("joint", 2)]
-        ok = ok and len(log) == len(issued)                                   # sync() only waited: no further collective
+            check("fused_backward/merged/launch_and_collective_order", issued == [("launch", ("fine", "coarse")), ("all_reduce", 2 * n)])
+            check("fused_backward/merged/issue_log", gs.issue_log[:1] == [("joint", 2)])
+        check("fused_backward/%s/sync_only_waited" % form, len(log) == len(issued))                # no further collective
         want = (world + 1) / 2.0
-        ok = ok and all(torch.allclose(p_.grad, torch.full_like(p_, want)) for p_ in fine.parameters())
-        ok = ok and all(torch.allclose(p_.grad, torch.full_like(p_, 3.0 * want)) for p_ in coarse.parameters())
+        check("fused_backward/%s/fine_averaged" % form, all(torch.allclose(p_.grad, torch.full_like(p_, want)) for p_ in fine.parameters()))
+        check("fused_backward/%s/coarse_averaged" % form,
+              all(torch.allclose(p_.grad, torch.full_like(p_, 3.0 * want)) for p_ in coarse.parameters()))
         gs.detach()
-    return bool(ok)
+
+
+def _sharded_render(check, rank, world, n_rays):
+    g = torch.Generator().manual_seed(7)
+    rays = torch.rand(n_rays, 8, generator=g)
+    with _patched("all_gather_into_tensor", _counting) as gathers:
+        out = parallel.render_sharded(_fake_render, rays)
+    ref = _fake_render(rays)
+    # every key comes back whole, through ONE collective per image (rgb + depth + opacity packed as the columns of one buffer)
+    check("render/every_key_whole", all(torch.equal(out[k], ref[k]) for k in ref))
+    check("render/one_gather_per_image", len(gathers) == 1)
+
+
+def _generic(check, rank, world):
+    """generic branch: per-rank grads r+1 -> mean (world+1)/2"""
+    m = _Tiny()
+    for p in m.parameters():
+        p.grad = torch.full_like(p, float(rank + 1))
+    parallel.GradSync([m]).sync()
+    want = (world + 1) / 2.0
+    check("generic/averaged", all(torch.allclose(p.grad, torch.full_like(p, want)) for p in m.parameters()))
+
+
+def _flat_and_alias(check, rank, world):
+    """flat branch: grads are views of one flat buffer (what ops.mlp_bwd hands autograd)"""
+    m = _Tiny()
+    flat = _base() * (rank + 1)
+    _adopt(m, flat)
+    m._flat_grad = flat
+    parallel.GradSync([m]).sync()
+    check("flat/averaged_in_place", torch.allclose(flat, _base() * (world + 1) / 2.0))
+    # and the parameters' .grad still alias the averaged buffer
+    check("flat/grads_still_alias", all(p.grad.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr() for p in m.parameters()))
+
+
+def _overlap(check, rank, world, m, gs):
+    """the fused backward announces a finished flat buffer through the grad-ready hook; the all-reduce is issued THEN (while
+    "the rest of backward" still runs) and sync() only waits and averages"""
+    want = (world + 1) / 2.0
+    flat = _base() * (rank + 1) + 1.0
+    m._flat_grad = flat
+    check("overlap/hook_attached", m._grad_ready_hook is not None)
+    m._grad_ready_hook(m, flat)                             # what models/mlp_autograd._param_grads does (p.grad still None)
+    _adopt(m, flat)
+    started = gs.started_early
+    gs.sync()
+    check("overlap/issued_from_hook", started == 1)
+    check("overlap/nothing_left_in_flight", not gs._inflight)
+    check("overlap/averaged", torch.allclose(flat, _base() * want + 1.0))
+
+
+def _hooks_off(check, rank, world, m, gs):
+    """hooks switched off (two-graph capture): nothing is issued early, sync() does the whole job"""
+    want = (world + 1) / 2.0
+    gs.hooks_enabled = False
+    _clear(m)
+    flat = m._flat_grad
+    flat.copy_(_base() * (rank + 1))
+    before = gs.started_early
+    m._grad_ready_hook(m, flat)
+    _adopt(m, flat)
+    check("hooks_off/issues_nothing", gs.started_early == before == 1)
+    gs.sync()
+    check("hooks_off/averaged", torch.allclose(flat, _base() * want))
+    gs.hooks_enabled = True
+
+
+def _accumulation(check, rank, world, m, gs):
+    """gradient accumulation: p.grad exists when the backward announces its buffer -> autograd ACCUMULATES the
+    views into p.grad, so no early collective may touch the buffer; sync() averages the accumulated p.grad"""
+    want = (world + 1) / 2.0
+    for p in m.parameters():
+        p.grad = torch.full_like(p, 10.0 * (rank + 1))
+    flat = _base() * (rank + 1)
+    m._flat_grad = flat
+    before = gs.started_early
+    m._grad_ready_hook(m, flat)
+    _accumulate(m, flat)
+    gs.sync()
+    check("accumulation/issues_nothing", gs.started_early == before)
+    check("accumulation/averaged", torch.allclose(_grads(m), _base() * want + 10.0 * want))
+
+
+def _two_backwards(check, rank, world, m, gs):
+    """two backwards before one sync(): the first buffer is all-reduced early, the second backward accumulates on top of it"""
+    want = (world + 1) / 2.0
+    _clear(m)
+    first = _base() * (rank + 1)
+    m._flat_grad = first
+    m._grad_ready_hook(m, first)
+    _adopt(m, first)
+    second = _base() * (rank + 1) * 2.0
+    m._flat_grad = second
+    m._grad_ready_hook(m, second)                           # waits for + finishes the first collective, issues nothing
+    _accumulate(m, second)
+    gs.sync()
+    check("two_backwards/averaged", torch.allclose(_grads(m), _base() * want * 3.0))
+
+
+def _copied_views_refused(check, rank, world, m, gs):
+    """autograd COPIED the announced views instead of adopting them: refused, never silently un-averaged"""
+    _clear(m)
+    flat = _base() * (rank + 1)
+    m._flat_grad = flat
+    m._grad_ready_hook(m, flat)
+    _adopt(m, flat.clone())
+    try:
+        gs.sync()
+        raised = False
+    except RuntimeError:
+        raised = True
+    check("copied_views/refused", raised)
+
+
+def _two_models(rank):
+    ms, flats = [], []
+    for k in range(2):
+        m = _Tiny()
+        fl = _base() * (rank + 1) * (k + 1)
+        _adopt(m, fl)
+        m._flat_grad = fl
+        ms.append(m)
+        flats.append(fl)
+    gs = parallel.GradSync(ms)
+    gs.hooks_enabled = False
+    gs._coalesce_backends = ("nccl", "gloo")
+    return gs, flats
+
+
+def _grouped(check, rank, world):
+    """round 5: the two-graph step's sync() issues the models' all-reduces as ONE grouped launch (RCCL: ncclGroupStart / End
+    through torch's coalescing manager).  Same branch driven over gloo here: one manager entry for both buffers, the values
+    of two separate calls; and when the grouped form raises, sync() falls back to one call per model for good."""
+    want = (world + 1) / 2.0
+    gs, flats = _two_models(rank)
+    with _patched("_coalescing_manager", _counting) as entered:
+        gs.sync()
+    check("grouped/ok/one_manager_entry", len(entered) == 1)
+    check("grouped/ok/stays_on", gs._coalesce)
+    check("grouped/ok/averaged", all(torch.allclose(f, _base() * want * (k + 1)) for k, f in enumerate(flats)))
+    # a stack WITHOUT the grouped form: the only reason to fall back
+    gs, flats = _two_models(rank)
+    with _patched("_coalescing_manager", _raising(NotImplementedError("no grouped collectives on this stack"))):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            gs.sync()
+    check("grouped/unavailable/switched_off", not gs._coalesce)
+    check("grouped/unavailable/averaged", all(torch.allclose(f, _base() * want * (k + 1)) for k, f in enumerate(flats)))
+    # (ADVICE r5) any OTHER error — a communicator error, a failure after a partial enqueue — is re-raised, never papered over by
+    # re-issuing the collectives one by one (they could run twice, or mismatch across the ranks): every rank raises alike here
+    gs, flats = _two_models(rank)
+    with _patched("_coalescing_manager", _raising(RuntimeError("communicator error"))):
+        try:
+            gs.sync()
+            raised = False
+        except RuntimeError:
+            raised = True
+    check("grouped/error/raised", raised)
+    check("grouped/error/stays_on", gs._coalesce)
+    check("grouped/error/nothing_reissued", all(torch.allclose(f, _base() * (rank + 1) * (k + 1)) for k, f in enumerate(flats)))
+
+
+def _joint_models(rank, scale):
+    ms = [_Tiny(), _Tiny()]
+    joint = torch.empty(2 * _N)
+    flats = [joint[k * _N:(k + 1) * _N] for k in range(2)]
+    for k, fl in enumerate(flats):
+        fl.copy_(_base() * (rank + 1) * (k + 1) * scale)
+        ms[k]._flat_grad = fl
+    return ms, flats
+
+
+def _joint(check, rank, world):
+    """round 6: the fused step's backward writes both models' flat buffers as consecutive slices of ONE allocation
+    (ops.mlp_bwd_multi) and announces them together; GradSync(form="merged") — the default — issues ONE all-reduce over the
+    joint buffer from that hook, and sync() only waits.  With the hooks off (the two-graph fallback) sync() itself sends the
+    joint range as one message: no coalescing manager involved."""
+    want = (world + 1) / 2.0
+    ms, flats = _joint_models(rank, 1.0)
+    gs = parallel.GradSync(ms)
+    check("joint/hook/merged_is_default", gs.form == "merged")
+    check("joint/hook/one_hook_for_all_models", ms[0]._grads_ready_hook is not None and ms[0]._grads_ready_hook == ms[1]._grads_ready_hook)
+    with _patched("all_reduce", _counting) as sent:
+        ms[0]._grads_ready_hook(ms, flats)                  # what models/train_step._TrainRender.backward does (p.grad still None)
+        check("joint/hook/one_message_over_joint_range", [t.numel() for t in sent] == [2 * _N])
+        check("joint/hook/issue_log", gs.issue_log == [("joint", 2)])
+        for m, fl in zip(ms, flats):
+            _adopt(m, fl)
+        gs.sync()
+        check("joint/hook/sync_only_waited", len(sent) == 1)
+    check("joint/hook/nothing_left_in_flight", not gs._inflight)
+    check("joint/hook/averaged", all(torch.allclose(f, _base() * want * (k + 1)) for k, f in enumerate(flats)))
+    # hooks off: sync() sends the joint range itself, as ONE message
+    ms, flats = _joint_models(rank, 2.0)
+    gs = parallel.GradSync(ms)
+    gs.hooks_enabled = False
+    gs._coalesce_backends = ("nccl", "gloo")
+    with _patched("all_reduce", _counting) as sent, _patched("_coalescing_manager", _counting) as entered:
+        ms[0]._grads_ready_hook(ms, flats)
+        for m, fl in zip(ms, flats):
+            _adopt(m, fl)
+        gs.sync()
+    check("joint/hooks_off/one_message_over_joint_range", [t.numel() for t in sent] == [2 * _N])
+    check("joint/hooks_off/no_coalescing_manager", len(entered) == 0)
+    check("joint/hooks_off/averaged", all(torch.allclose(f, _base() * want * (k + 1) * 2.0) for k, f in enumerate(flats)))
+    # ... whatever the order the models are listed in: the real backward lays the FINE model's buffer first while NeRFSystem
+    # lists the coarse model first (on the GPU: tests/test_gpu_world2.py) — still ONE message over the joint range
+    ms, flats = _joint_models(rank, 3.0)
+    gs = parallel.GradSync(ms[::-1])
+    gs.hooks_enabled = False
+    with _patched("all_reduce", _counting) as sent:
+        for m, fl in zip(ms, flats):
+            _adopt(m, fl)
+        gs.sync()
+    check("joint/reversed/one_message_over_joint_range", [t.numel() for t in sent] == [2 * _N])
+    check("joint/reversed/averaged", all(torch.allclose(f, _base() * want * (k + 1) * 3.0) for k, f in enumerate(flats)))
+    # gradient accumulation under the joint hook: nothing is issued early, sync() averages the accumulated p.grad
+    ms, flats = _joint_models(rank, 1.0)
+    gs = parallel.GradSync(ms)
+    for m in ms:
+        for p in m.parameters():
+            p.grad = torch.full_like(p, 10.0 * (rank + 1))
+    with _patched("all_reduce", _counting) as sent:
+        ms[0]._grads_ready_hook(ms, flats)
+    check("joint/accumulation/issues_nothing", len(sent) == 0)
+    for m, fl in zip(ms, flats):
+        _accumulate(m, fl)
+    gs.sync()
+    check("joint/accumulation/averaged",
+          all(torch.allclose(_grads(m), _base() * want * (k + 1) + 10.0 * want) for k, m in enumerate(ms)))
 
 
 def _worker(rank, world, port, n_rays, q):
+    """Every scenario runs on every rank, in this order (the same sequence of collectives on both: a rank that skipped one
+    would leave its peer waiting in gloo)."""
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        g = torch.Generator().manual_seed(7)
-        rays = torch.rand(n_rays, 8, generator=g)
-        calls = {"n": 0}
-        real_gather = dist.all_gather_into_tensor
-
-        def counting_gather(*a, **kw):
-            calls["n"] += 1
-            return real_gather(*a, **kw)
-        dist.all_gather_into_tensor = counting_gather
-        try:
-            out = parallel.render_sharded(_fake_render, rays)
-        finally:
-            dist.all_gather_into_tensor = real_gather
-        ref = _fake_render(rays)
-        # every key comes back whole, through ONE collective per image (rgb + depth + opacity packed as the columns of one buffer)
-        ok_render = all(torch.equal(out[k], ref[k]) for k in ref) and calls["n"] == 1
-
-        # --- GradSync, generic branch: per-rank grads r+1 -> mean (world+1)/2
-        m = _Tiny()
-        for p in m.parameters():
-            p.grad = torch.full_like(p, float(rank + 1))
-        parallel.GradSync([m]).sync()
-        want = (world + 1) / 2.0
-        ok_generic = all(torch.allclose(p.grad, torch.full_like(p, want)) for p in m.parameters())
-
-        # --- GradSync, flat branch: grads are views of one flat buffer (what ops.mlp_bwd hands autograd)
-        m2 = _Tiny()
-        sizes = [p.numel() for p in m2.parameters()]
-        flat = torch.arange(sum(sizes), dtype=torch.float32) * (rank + 1)
-        off = 0
-        for p, sz in zip(m2.parameters(), sizes):
-            p.grad = flat[off:off + sz].view_as(p)
-            off += sz
-        m2._flat_grad = flat
-        parallel.GradSync([m2]).sync()
-        ok_flat = torch.allclose(flat, torch.arange(sum(sizes), dtype=torch.float32) * want)
-        # and the parameters' .grad still alias the averaged buffer
-        ok_alias = all(p.grad.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr() for p in m2.parameters())
-        # --- GradSync, overlap: the fused backward announces a finished flat buffer through the grad-ready hook; the
-        # all-reduce is issued THEN (while "the rest of backward" still runs) and sync() only waits and averages
-        m3 = _Tiny()
-        gs = parallel.GradSync([m3])
-        base3 = torch.arange(sum(sizes), dtype=torch.float32)
-
-        def adopt(model, flat_):                            # what autograd does with the views the backward returns
-            off_ = 0
-            for p_, sz_ in zip(model.parameters(), sizes):
-                p_.grad = flat_[off_:off_ + sz_].view_as(p_)
-                off_ += sz_
-        flat3 = base3 * (rank + 1) + 1.0
-        m3._flat_grad = flat3
-        assert m3._grad_ready_hook is not None
-        m3._grad_ready_hook(m3, flat3)                      # what models/mlp_autograd._param_grads does (p.grad still None)
-        adopt(m3, flat3)
-        started = gs.started_early
-        gs.sync()
-        ok_overlap = started == 1 and not gs._inflight and torch.allclose(flat3, base3 * want + 1.0)
-        # hooks switched off (two-graph capture): nothing is issued early, sync() does the whole job
-        gs.hooks_enabled = False
-        for p_ in m3.parameters():
-            p_.grad = None
-        flat3.copy_(base3 * (rank + 1))
-        m3._grad_ready_hook(m3, flat3)
-        adopt(m3, flat3)
-        ok_overlap = ok_overlap and gs.started_early == 1
-        gs.sync()
-        ok_overlap = ok_overlap and torch.allclose(flat3, base3 * want)
-        gs.hooks_enabled = True
-        # gradient accumulation: p.grad exists when the backward announces its buffer -> autograd ACCUMULATES the
-        # views into p.grad, so no early collective may touch the buffer; sync() averages the accumulated p.grad
-        acc = [torch.full_like(p_, 10.0 * (rank + 1)) for p_ in m3.parameters()]
-        for p_, a_ in zip(m3.parameters(), acc):
-            p_.grad = a_.clone()
-        flat4 = base3 * (rank + 1)
-        m3._flat_grad = flat4
-        before = gs.started_early
-        m3._grad_ready_hook(m3, flat4)
-        off = 0
-        for p_, sz in zip(m3.parameters(), sizes):
-            p_.grad += flat4[off:off + sz].view_as(p_)
-            off += sz
-        gs.sync()
-        got = torch.cat([p_.grad.reshape(-1) for p_ in m3.parameters()])
-        ok_overlap = ok_overlap and gs.started_early == before and torch.allclose(got, base3 * want + 10.0 * want)
-        # two backwards before one sync(): the first buffer is all-reduced early, the second backward accumulates on top of it
-        for p_ in m3.parameters():
-            p_.grad = None
-        flat5 = base3 * (rank + 1)
-        m3._flat_grad = flat5
-        m3._grad_ready_hook(m3, flat5)
-        adopt(m3, flat5)
-        flat6 = base3 * (rank + 1) * 2.0
-        m3._flat_grad = flat6
-        m3._grad_ready_hook(m3, flat6)                      # waits for + finishes the first collective, issues nothing
-        off = 0
-        for p_, sz in zip(m3.parameters(), sizes):
-            p_.grad += flat6[off:off + sz].view_as(p_)
-            off += sz
-        gs.sync()
-        got = torch.cat([p_.grad.reshape(-1) for p_ in m3.parameters()])
-        ok_overlap = ok_overlap and torch.allclose(got, base3 * want * 3.0)
-        # autograd COPIED the announced views instead of adopting them: refused, never silently un-averaged
-        for p_ in m3.parameters():
-            p_.grad = None
-        flat7 = base3 * (rank + 1)
-        m3._flat_grad = flat7
-        m3._grad_ready_hook(m3, flat7)
-        adopt(m3, flat7.clone())
-        try:
-            gs.sync()
-            ok_overlap = False
-        except RuntimeError:
-            pass
-
-        # --- round 5: the two-graph step's sync() issues the models' all-reduces as ONE grouped launch (RCCL: ncclGroupStart / End
-        # through torch's coalescing manager).  Same branch driven over gloo here: one manager entry for both buffers, the values
-        # of two separate calls; and when the grouped form raises, sync() falls back to one call per model for good.
-        def two_models():
-            ms_, flats_ = [], []
-            for k in range(2):
-                mm = _Tiny()
-                fl = base3 * (rank + 1) * (k + 1)
-                adopt(mm, fl)
-                mm._flat_grad = fl
-                ms_.append(mm)
-                flats_.append(fl)
-            return ms_, flats_
-        ms8, flats8 = two_models()
-        gs8 = parallel.GradSync(ms8)
-        gs8.hooks_enabled = False
-        gs8._coalesce_backends = ("nccl", "gloo")
-        entered = {"n": 0}
-        real_cm = dist._coalescing_manager
-
-        def counting_cm(*a, **kw):
-            entered["n"] += 1
-            return real_cm(*a, **kw)
-        dist._coalescing_manager = counting_cm
-        try:
-            gs8.sync()
-        finally:
-            dist._coalescing_manager = real_cm
-        ok_grouped = entered["n"] == 1 and gs8._coalesce and all(torch.allclose(f, base3 * want * (k + 1)) for k, f in enumerate(flats8))
-
-        def broken_cm(*a, **kw):                                # a stack WITHOUT the grouped form: the only reason to fall back
-            raise NotImplementedError("no grouped collectives on this stack")
-        ms9, flats9 = two_models()
-        gs9 = parallel.GradSync(ms9)
-        gs9.hooks_enabled = False
-        gs9._coalesce_backends = ("nccl", "gloo")
-        dist._coalescing_manager = broken_cm
-        try:
-            import warnings
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                gs9.sync()
-        finally:
-            dist._coalescing_manager = real_cm
-        ok_grouped = ok_grouped and not gs9._coalesce and all(torch.allclose(f, base3 * want * (k + 1)) for k, f in enumerate(flats9))
-        #  any OTHER error — a communicator error, a failure after a partial enqueue — is re-raised, never papered over by
-        # re-issuing the collectives one by one (they could run twice, or mismatch across the ranks): every rank raises alike here
-        def failing_cm(*a, **kw):
-            raise RuntimeError("communicator error")
-        ms10, flats10 = two_models()
-        gs10 = parallel.GradSync(ms10)
-        gs10.hooks_enabled = False
-        gs10._coalesce_backends = ("nccl", "gloo")
-        dist._coalescing_manager = failing_cm
-        try:
-            gs10.sync()
-            ok_grouped = False
-        except RuntimeError:
-            ok_grouped = ok_grouped and gs10._coalesce and all(torch.allclose(f, base3 * (rank + 1) * (k + 1)) for k, f in enumerate(flats10))
-        finally:
-            dist._coalescing_manager = real_cm
-        ok_overlap = ok_overlap and ok_grouped
-
-        # --- round 6: the fused step's backward writes both models' flat buffers as consecutive slices of ONE allocation
-        # (ops.mlp_bwd_multi) and announces them together; GradSync(form="merged") — the default — issues ONE all-reduce over the
-        # joint buffer from that hook, and sync() only waits.  With the hooks off (the two-graph fallback) sync() itself sends the
-        # joint range as one message: no coalescing manager involved.
-        def joint_models(scale):
-            ms_ = [_Tiny(), _Tiny()]
-            n_ = sum(sizes)
-            joint_ = torch.empty(2 * n_)
-            flats_ = [joint_[k * n_:(k + 1) * n_] for k in range(2)]
-            for k, fl in enumerate(flats_):
-                fl.copy_(base3 * (rank + 1) * (k + 1) * scale)
-                ms_[k]._flat_grad = fl
-            return ms_, flats_, joint_
-        ms11, flats11, joint11 = joint_models(1.0)
-        gs11 = parallel.GradSync(ms11)
-        calls11 = {"n": 0, "numel": []}
-        real_ar = dist.all_reduce
-
-        def counting_ar(t, *a_, **kw_):
-            calls11["n"] += 1
-            calls11["numel"].append(t.numel())
-            return real_ar(t, *a_, **kw_)
-        dist.all_reduce = counting_ar
-        try:
-            ok_joint = gs11.form == "merged" and ms11[0]._grads_ready_hook is not None and ms11[0]._grads_ready_hook == ms11[1]._grads_ready_hook
-            ms11[0]._grads_ready_hook(ms11, flats11)             # what models/train_step._TrainRender.backward does (p.grad still None)
-            ok_joint = ok_joint and calls11["n"] == 1 and calls11["numel"] == [2 * sum(sizes)] and gs11.issue_log == [("joint", 2)]
-            for mm, fl in zip(ms11, flats11):
-                adopt(mm, fl)
-            gs11.sync()
-            ok_joint = ok_joint and calls11["n"] == 1 and not gs11._inflight       # sync() only waited
-            ok_joint = ok_joint and all(torch.allclose(f, base3 * want * (k + 1)) for k, f in enumerate(flats11))
-            # hooks off: sync() sends the joint range itself, as ONE message
-            ms12, flats12, _ = joint_models(2.0)
-            gs12 = parallel.GradSync(ms12)
-            gs12.hooks_enabled = False
-            gs12._coalesce_backends = ("nccl", "gloo")
-            entered["n"] = 0
-            dist._coalescing_manager = counting_cm
-            calls11["n"], calls11["numel"] = 0, []
-            ms12[0]._grads_ready_hook(ms12, flats12)
-            for mm, fl in zip(ms12, flats12):
-                adopt(mm, fl)
-            gs12.sync()
-            ok_joint = ok_joint and calls11["n"] == 1 and calls11["numel"] == [2 * sum(sizes)] and entered["n"] == 0
-            ok_joint = ok_joint and all(torch.allclose(f, base3 * want * (k + 1) * 2.0) for k, f in enumerate(flats12))
-            # ... whatever the order the models are listed in: the real backward lays the FINE model's buffer first while NeRFSystem
-            # lists the coarse model first (on the GPU: tests/test_gpu_world2.py) — still ONE message over the joint range
-            ms14, flats14, _ = joint_models(3.0)
-            gs14 = parallel.GradSync(ms14[::-1])
-            gs14.hooks_enabled = False
-            calls11["n"], calls11["numel"] = 0, []
-            for mm, fl in zip(ms14, flats14):
-                adopt(mm, fl)
-            gs14.sync()
-            ok_joint = ok_joint and calls11["numel"] == [2 * sum(sizes)]
-            ok_joint = ok_joint and all(torch.allclose(f, base3 * want * (k + 1) * 3.0) for k, f in enumerate(flats14))
-            # gradient accumulation under the joint hook: nothing is issued early, sync() averages the accumulated p.grad
-            ms13, flats13, _ = joint_models(1.0)
-            gs13 = parallel.GradSync(ms13)
-            for mm in ms13:
-                for p_ in mm.parameters():
-                    p_.grad = torch.full_like(p_, 10.0 * (rank + 1))
-            calls11["n"] = 0
-            ms13[0]._grads_ready_hook(ms13, flats13)
-            ok_joint = ok_joint and calls11["n"] == 0
-            for mm, fl in zip(ms13, flats13):
-                off = 0
-                for p_, sz in zip(mm.parameters(), sizes):
-                    p_.grad += fl[off:off + sz].view_as(p_)
-                    off += sz
-            gs13.sync()
-            got13 = [torch.cat([p_.grad.reshape(-1) for p_ in mm.parameters()]) for mm in ms13]
-            ok_joint = ok_joint and all(torch.allclose(g_, base3 * want * (k + 1) + 10.0 * want) for k, g_ in enumerate(got13))
-        finally:
-            dist.all_reduce = real_ar
-            dist._coalescing_manager = real_cm
-        ok_overlap = ok_overlap and ok_joint
-        ok_overlap = ok_overlap and _fused_backward_issue_order(rank, world)
-
-        # --- the N>1 training step's host logic (system.GraphedTrainStep): eager warm-up steps, capture of
-        # [forward+backward] and [optimizer] as two graphs with the collective issued eagerly in between, replays,
-        # re-capture on a learning-rate change — with a recording stand-in for the hipGraph backend.
-        ok_step = _graphed_step_host_logic(rank, world)
-        q.put((rank, ok_render, ok_generic, ok_flat, ok_alias, ok_overlap, ok_step))
+        check = _Checks()
+        _sharded_render(check, rank, world, n_rays)
+        _generic(check, rank, world)
+        _flat_and_alias(check, rank, world)
+        m = _Tiny()                                         # one model and one GradSync through the hook scenarios, as a training
+        gs = parallel.GradSync([m])                         # loop has: each starts from what the one before left behind
+        for scenario in (_overlap, _hooks_off, _accumulation, _two_backwards, _copied_views_refused):
+            scenario(check, rank, world, m, gs)
+        _grouped(check, rank, world)
+        _joint(check, rank, world)
+        _fused_backward_issue_order(check, rank, world)
+        _graphed_step_host_logic(check, rank, world)
+        q.put((rank, check.results))
     finally:
         dist.destroy_process_group()
 
@@ -521,8 +576,10 @@ def test_world2_gloo_sharding_and_gradsync(n_rays):
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    for r in res:
-        assert all(r[1:]), r
+    failed = sorted("rank %d: %s" % (rank, name) for rank, results in res for name, ok in results.items() if not ok)
+    print("\n".join(failed))
+    assert not failed, failed
+    assert all(len(results) == len(res[0][1]) > 40 for _, results in res)      # every rank ran every check
 
 
 def test_shard_bounds_cover_exactly():
