@@ -267,7 +267,8 @@ def _replica_draws(specs, device, generator, batch, pack):
             check(launch(seed, off, None), "nerfhip_torch_draws")
             g.set_offset(off + int(inc.value))
         if pack is not None:
-            ops.mark_packed(pack[0])
+            for m in pack[0]:
+                m.images_packed()
     return outs
 
 

@@ -10,14 +10,58 @@ import torch
 from .. import ops
 
 
+# -- the gradient hand-off: what a backward leaves on a module for parallel.GradSync and optim's flat optimizers.  Plain attributes
+# on any nn.Module (GradSync also serves modules that are not NeRF), named in this module only.
+def set_grad_hooks(model, ready, joint):
+    """ready(model, flat) / joint(models, flats), or None: what grads_ready calls for this model"""
+    model._grad_ready_hook, model._grads_ready_hook = ready, joint
+
+
+def clear_grad_hooks(model, ready, joint):
+    """take back the hooks that are still `ready` / `joint` (another owner's stay)"""
+    if getattr(model, "_grad_ready_hook", None) == ready:
+        model._grad_ready_hook = None
+    if getattr(model, "_grads_ready_hook", None) == joint:
+        model._grads_ready_hook = None
+
+
+def flat_grad(model):
+    """the flat buffer the model's last backward wrote its gradients into (None: none yet, or since flat_grad_reset)"""
+    return getattr(model, "_flat_grad", None)
+
+
+def flat_grad_reset(model):
+    model._flat_grad = None
+
+
+def grad_hooks(models):
+    """-> (any model has a grad-ready hook, the ONE joint hook all of them share or None): which of its three cases grads_ready will
+    take — _TrainRender.backward chooses its launch groups by it ahead of its launches"""
+    hooked = any(getattr(m, "_grad_ready_hook", None) is not None for m in models)
+    joint = getattr(models[0], "_grads_ready_hook", None) if hooked else None
+    shared = joint is not None and all(getattr(m, "_grads_ready_hook", None) == joint for m in models)
+    return hooked, joint if shared else None
+
+
+def grads_ready(models, flats):
+    """A backward calls this when the flat gradient buffers `flats` of `models` are complete, before autograd hands their views to
+    the parameters: records each model's buffer, then calls the joint hook ONCE if all share one, else each model's own where it
+    has one (parallel.GradSync: the all-reduce starts while autograd keeps going)."""
+    for m, flat in zip(models, flats):
+        m._flat_grad = flat
+    joint = grad_hooks(models)[1]
+    if joint is not None:
+        return joint(models, flats)
+    for m, flat in zip(models, flats):
+        if getattr(m, "_grad_ready_hook", None) is not None:
+            m._grad_ready_hook(m, flat)
+
+
 def _param_grads(model, out, acts, dtype, g_out, packed_bwd, workspace=None):
     """nerfhip_mlp_bwd (chain + dW + reduce kernels) -> gradients in `flat_params()` order.  `packed_bwd`: the W^T image the
     forward packed together with its own (NeRF.packed_weights_train)."""
     gw, gb, flat = ops.mlp_bwd(g_out, out, packed_bwd, acts, dtype, workspace=workspace)
-    model._flat_grad = flat          # contiguous view of this step's gradients (parallel.GradSync / FlatAdam use it)
-    hook = getattr(model, "_grad_ready_hook", None)
-    if hook is not None:             # parallel.GradSync: start this model's all-reduce while autograd keeps going
-        hook(model, flat)
+    grads_ready([model], [flat])
     need = [p.requires_grad for p in model.flat_params()]
     return [g if nd else None for g, nd in zip(gw + gb, need)]
 
@@ -36,7 +80,7 @@ class _MLPRays(torch.autograd.Function):
         packed, packed_bwd = model.packed_weights_train(dtype)
         out = ops.mlp_fwd_rays(rays, z, packed, False, dtype, save=acts)
         ctx.model, ctx.dtype, ctx.acts, ctx.packed_bwd = model, dtype, acts, packed_bwd
-        ctx.serial = model._packed_serial
+        ctx.serial = model.pack_serial()
         ctx.save_for_backward(out)
         return out
 
@@ -63,7 +107,7 @@ class _MLPEmbedded(torch.autograd.Function):
         packed, packed_bwd = model.packed_weights_train(dtype)
         out = ops.mlp_fwd_embedded(x, packed, False, dtype, save=acts)
         ctx.model, ctx.dtype, ctx.acts, ctx.packed_bwd = model, dtype, acts, packed_bwd
-        ctx.serial = model._packed_serial
+        ctx.serial = model.pack_serial()
         ctx.save_for_backward(out)
         return out
 

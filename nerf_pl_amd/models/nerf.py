@@ -4,6 +4,8 @@ Same classes, constructor signatures, attributes and `state_dict` layout as the 
 (models/nerf.py:4-124) so checkpoints, optimizers and DDP see an ordinary nn.Module; `forward`
 dispatches to the HIP kernels of libnerfhip (posenc / fused MFMA MLP) instead of ATen op chains.
 """
+import weakref
+
 import torch
 from torch import nn
 
@@ -50,6 +52,12 @@ class Embedding(nn.Module):
 
 
 class NeRF(nn.Module):
+    # Weight-image freshness — do the packed MFMA weight images still belong to the current weights? — is this class's alone: the
+    # state, every transition (the methods below) and, for a pack made ahead of a step, pack_ticket / ticket_fresh.
+    _weights_serial = 0         # advanced by weights_changed()
+    _packed_serial = None       # the weights' serial the training images were packed from; None = never packed
+    _serial_tracked = None      # weak reference to the optimizer that announces every update of these weights, or None
+
     def __init__(self, D=8, W=256, in_channels_xyz=63, in_channels_dir=27, skips=[4]):
         """Reference: models/nerf.py:42-81 (identical submodule names => identical state_dict keys)."""
         super(NeRF, self).__init__()
@@ -74,12 +82,39 @@ class NeRF(nn.Module):
         # --- MI355X specifics (not part of state_dict) ---
         self.mlp_dtype = default_mlp_dtype()    # 'fp32' (parity) | 'bf16' | 'bf16_f8' (roofline); a non-default shape runs
                                                 # layer by layer (models/layered.py) and reads 'bf16_f8' as 'bf16'
-        self._packed_cache = {}
+        self._arg_tables = None                 # (parameter addresses, weight pointer table, bias pointer table)
+        self._fwd_images, self._bwd_images = {}, {}     # forward / W^T image buffer by dtype
         # weights replaced wholesale (load_ckpt, utils/__init__.py:55-76): weight images packed ahead of a step are stale
-        self.register_load_state_dict_post_hook(lambda module, _incompatible: module._bump_weights_serial())
+        self.register_load_state_dict_post_hook(lambda module, _incompatible: module.weights_changed())
 
-    def _bump_weights_serial(self):
-        self._weights_serial = getattr(self, "_weights_serial", 0) + 1
+    # -- weight-image freshness ----------------------------------------------------------------
+    def weights_changed(self):
+        """images packed before this point are stale (load_state_dict above; optim's flat optimizers, for each of their updates)"""
+        self._weights_serial += 1
+
+    def weights_serial(self):
+        return self._weights_serial
+
+    def announced_by(self, optimizer):
+        """`optimizer` calls weights_changed() for every update it makes.  A weak reference: a dead optimizer vouches for nothing."""
+        self._serial_tracked = weakref.ref(optimizer)
+
+    def announced(self):
+        return self._serial_tracked is not None and self._serial_tracked() is not None
+
+    def images_packed(self):
+        """the training images were just packed from the current weights"""
+        self._packed_serial = self._weights_serial
+
+    def pack_serial(self):
+        """what a training forward notes for its backward's check_pack_serial"""
+        return self._packed_serial
+
+    def check_pack_serial(self, serial):
+        """backward side of packed_weights_train: the W^T image must still be the one packed from the weights of `serial`"""
+        if self._packed_serial is None or self._packed_serial != serial:
+            raise RuntimeError("the W^T image this backward needs was re-packed from UPDATED weights by a later training forward of "
+                               "the same model (an optimizer stepped between this graph's forward and its backward)")
 
     # -- fused-kernel plumbing -----------------------------------------------------------------
     def is_default_arch(self):
@@ -106,26 +141,20 @@ class NeRF(nn.Module):
         storage moved (host-side cost matters: a training step re-packs four times and lasts ~1.7 ms)."""
         ps = self.flat_params()
         key = tuple(p.data_ptr() for p in ps)
-        hit = self._packed_cache.get("args")
+        hit = self._arg_tables
         if hit is None or hit[0] != key:
-            hit = (key,) + ops.pack_arg_tables(ps[:12], ps[12:])
-            self._packed_cache["args"] = hit
+            hit = self._arg_tables = (key,) + ops.pack_arg_tables(ps[:12], ps[12:])
         return hit[1], hit[2], ps[0].device
 
     def _require_default_arch(self):
         if not self.is_default_arch():
             raise NotImplementedError(ops.DEFAULT_ARCH_ONLY)
 
-    def _fwd_buffer(self, dtype, dev):
-        buf = self._packed_cache.get(dtype)
+    @staticmethod
+    def _buffer(images, nbytes, dtype, dev):
+        buf = images.get(dtype)
         if buf is None or buf.device != dev:
-            buf = self._packed_cache[dtype] = torch.empty(ops.packed_bytes(dtype), device=dev, dtype=torch.uint8)
-        return buf
-
-    def _bwd_buffer(self, dtype, dev):
-        buf = self._packed_cache.get(("bwd", dtype))
-        if buf is None or buf.device != dev:
-            buf = self._packed_cache[("bwd", dtype)] = torch.empty(ops.packed_bwd_bytes(dtype), device=dev, dtype=torch.uint8)
+            buf = images[dtype] = torch.empty(nbytes(dtype), device=dev, dtype=torch.uint8)
         return buf
 
     def packed_weights(self, dtype=None):
@@ -138,7 +167,7 @@ class NeRF(nn.Module):
         self._require_default_arch()
         dtype = dtype or self.mlp_dtype
         wp, bp, dev = self._pack_args()
-        buf = self._fwd_buffer(dtype, dev)
+        buf = self._buffer(self._fwd_images, ops.packed_bytes, dtype, dev)
         ops.pack_weights_raw(wp, bp, buf, dtype)
         return buf
 
@@ -146,33 +175,28 @@ class NeRF(nn.Module):
         """W^T stream for the backward chain + the fp32 fold block (same policy as packed_weights)."""
         dtype = dtype or self.mlp_dtype
         wp, bp, dev = self._pack_args()
-        buf = self._bwd_buffer(dtype, dev)
+        buf = self._buffer(self._bwd_images, ops.packed_bwd_bytes, dtype, dev)
         ops.pack_weights_bwd_raw(wp, bp, buf, dtype)
         return buf
 
     def train_buffers(self, dtype, dev):
         """(forward image buffer, W^T image buffer) of this model, allocated once per (dtype, device)."""
-        return self._fwd_buffer(dtype, dev), self._bwd_buffer(dtype, dev)
+        return (self._buffer(self._fwd_images, ops.packed_bytes, dtype, dev),
+                self._buffer(self._bwd_images, ops.packed_bwd_bytes, dtype, dev))
 
     def packed_weights_train(self, dtype=None):
         """(forward image, W^T image) of the current parameters in ONE launch: a training forward packs both, its backward
         reuses the second.  The images live in ONE buffer per model: a later training forward of the same model re-packs them.
         That is harmless while the weights are unchanged (identical images) and WRONG if an optimizer stepped in between —
         PyTorch raises for its own saved tensors in that situation; here it is detected only for optimizers that announce their
-        updates (FlatAdam bumps `_weights_serial`; `check_pack_serial` in the backward), not for foreign in-place updates."""
+        updates (FlatAdam calls `weights_changed`; `check_pack_serial` in the backward), not for foreign in-place updates."""
         self._require_default_arch()
         dtype = dtype or self.mlp_dtype
         wp, bp, dev = self._pack_args()
         buf, bwd = self.train_buffers(dtype, dev)
         ops.pack_weights_train_raw(wp, bp, buf, bwd, dtype)
-        self._packed_serial = getattr(self, "_weights_serial", 0)
+        self.images_packed()
         return buf, bwd
-
-    def check_pack_serial(self, serial):
-        """backward side of packed_weights_train: the W^T image must still be the one packed from the weights of `serial`"""
-        if getattr(self, "_packed_serial", 0) != serial:
-            raise RuntimeError("the W^T image this backward needs was re-packed from UPDATED weights by a later training forward of "
-                               "the same model (an optimizer stepped between this graph's forward and its backward)")
 
     def forward(self, x, sigma_only=False):
         """x: (B, 63+27) embedded position+direction, or (B, 63) when sigma_only.
@@ -185,3 +209,17 @@ class NeRF(nn.Module):
             return out.reshape(*lead, out.shape[-1])
         from .mlp_autograd import mlp_embedded
         return mlp_embedded(self, x, bool(sigma_only))
+
+
+def pack_ticket(models, dtype):
+    """What a pack of `models`' training images made AHEAD of a step (RayStore.sample(pack_models=...)) hands to that step as
+    batch['packed'].  Opaque to everyone but ticket_fresh."""
+    return tuple(id(m) for m in models), dtype, tuple(m._packed_serial for m in models)
+
+
+def ticket_fresh(ticket, models, dtype):
+    """The images the ticket stands for are still those of `models`' current weights in `dtype`: same models in the same order,
+    same dtype, and for every model neither the weights nor the images have moved since — which only a live optimizer that
+    ANNOUNCES its updates can vouch for (under any other the serials never move: not fresh, the step packs again)."""
+    return (ticket is not None and ticket[0] == tuple(id(m) for m in models) and ticket[1] == dtype
+            and all(m.announced() and m._weights_serial == sr and m._packed_serial == sr for m, sr in zip(models, ticket[2])))

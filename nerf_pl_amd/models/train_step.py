@@ -27,6 +27,8 @@ import numpy as np
 import torch
 
 from .. import ops
+from .mlp_autograd import grad_hooks, grads_ready
+from .nerf import ticket_fresh
 
 
 def fusable(models, embeddings, loss_mod):
@@ -55,13 +57,6 @@ def _forward_launches(models, rays, rgbs, S, N, dtype, use_disp, perturb, pertur
         entries = [(g_raw_c, raw_c, packs[0][1], acts_c)]
         outs = [rgb_c, depth_c, opac_c]
     return outs, entries, out3
-
-
-def _tracked(model):
-    """the model's weights are updated by a LIVE optimizer that announces its updates (optim.FlatAdam marks the model with a weak
-    reference to itself); load_state_dict bumps the serial on its own (models/nerf.py)"""
-    ref = getattr(model, "_serial_tracked", None)
-    return ref is not None and ref() is not None
 
 
 _regen_enc = os.environ.get("NERFHIP_REGEN_ENC", "0") == "1"
@@ -103,12 +98,10 @@ class _TrainRender(torch.autograd.Function):
             raise ValueError("render_rays_train: noise_std != 0 needs the noise draws")
         # weight images: the batch's launch packed them (RayStore.sample(pack_models=...)) and the weights have not moved since —
         # else ONE pack launch for both models here
-        # (only models whose optimizer ANNOUNCES its updates — FlatAdam bumps `_weights_serial` and marks `_serial_tracked` — can
-        # vouch for a pack made before this call; under any other optimizer the serials never move and the images are re-packed)
-        fresh = (packed is not None and packed[0] == tuple(id(m) for m in models) and packed[1] == dtype
-                 and all(_tracked(m) and getattr(m, "_weights_serial", 0) == sr
-                         and getattr(m, "_packed_serial", None) == sr for m, sr in zip(models, packed[2])))
-        packs = [m.train_buffers(dtype, dev) for m in models] if fresh else ops.pack_models_train(models, dtype)
+        # (only models whose optimizer ANNOUNCES its updates — NeRF.announced_by / weights_changed — can vouch for a pack made
+        # before this call; under any other optimizer the serials never move and the images are re-packed)
+        packs = ([m.train_buffers(dtype, dev) for m in models] if ticket_fresh(packed, models, dtype)
+                 else ops.pack_models_train(models, dtype))
         # d mean((rgb - t)^2) / d rgb = (rgb - t) * (2 / n), the quotient formed in fp32 like nerfhip_mse_psnr's `2.0f / (float)n`
         gscale = float(np.float32(2.0) / np.float32(3 * B))
         acts_c = ops.alloc_acts(B * S, dtype, dev)
@@ -134,7 +127,7 @@ class _TrainRender(torch.autograd.Function):
         ctx.models = [models[1], models[0]] if N > 0 else [models[0]]
         ctx.entries, ctx.dtype, ctx.adam = entries, dtype, adam
         ctx.n_params = [len(m.flat_params()) for m in models]
-        ctx.serials = [m._packed_serial for m in ctx.models]
+        ctx.serials = [m.pack_serial() for m in ctx.models]
         ctx.mark_non_differentiable(out3, *outs)
         ctx.set_materialize_grads(False)
         return (out3[0], out3) + tuple(outs)
@@ -151,9 +144,7 @@ class _TrainRender(torch.autograd.Function):
         models, dtype = ctx.models, ctx.dtype
         for m, serial in zip(models, ctx.serials):
             m.check_pack_serial(serial)
-        hooked = any(getattr(m, "_grad_ready_hook", None) is not None for m in models)
-        joint_hook = getattr(models[0], "_grads_ready_hook", None) if hooked else None
-        merged = joint_hook is not None and all(getattr(m, "_grads_ready_hook", None) == joint_hook for m in models)
+        hooked, joint_hook = grad_hooks(models)
         adam = None
         if not hooked:
             # Adam inside the reduce kernel only when these gradients ARE the step's gradients: with gradients already accumulated
@@ -167,17 +158,11 @@ class _TrainRender(torch.autograd.Function):
         # first, so that the fine model's all-reduce travels while the coarse model's backward still runs.  (Measured at world 1:
         # the per-model form costs 7.6 % of the step before any wire time — two dW launches fill the chip worse than one; a single
         # 4.77 MB all-reduce exposes less than that.)
-        groups = [[k] for k in range(n_models)] if hooked and not merged else [list(range(n_models))]
+        groups = [[k] for k in range(n_models)] if hooked and joint_hook is None else [list(range(n_models))]
         grads = []
         for group in groups:
-            ms = [models[k] for k in group]
             got = ops.mlp_bwd_multi([entries[k] for k in group], dtype, adam=adam, g_scale=g_scale)
-            for m, g in zip(ms, got):
-                m._flat_grad = g[2]
-            if merged:
-                joint_hook(ms, [g[2] for g in got])
-            elif hooked:
-                ms[0]._grad_ready_hook(ms[0], got[0][2])
+            grads_ready([models[k] for k in group], [g[2] for g in got])
             grads += got
         if adam is not None:
             ctx.adam.applied_in_backward(models)

@@ -721,12 +721,6 @@ def pack_tables(models, dtype):
     return W, Bv, P, Pb, bufs
 
 
-def mark_packed(models):
-    """the images just packed are those of the models' current weights (NeRF.check_pack_serial / train_step's freshness test)"""
-    for m in models:
-        m._packed_serial = getattr(m, "_weights_serial", 0)
-
-
 def pack_models_train(models, dtype):
     """Forward + W^T images of every model in ONE launch (nerfhip_mlp_pack_weights_train_multi).  Returns [(packed, packed_bwd)]
     in the models' cached buffers (NeRF.packed_weights_train's)."""
@@ -734,7 +728,8 @@ def pack_models_train(models, dtype):
     with torch.cuda.device(bufs[0][0].device):
         check(_lib.load().nerfhip_mlp_pack_weights_train_multi(W, Bv, P, Pb, len(models), mlp_dtype_code(dtype), stream_ptr()),
               "nerfhip_mlp_pack_weights_train_multi")
-    mark_packed(models)
+    for m in models:
+        m.images_packed()
     return bufs
 
 

@@ -18,12 +18,13 @@ same device-resident step counter — the rectification term depends on the step
 the device — and the per-parameter `state_dict()` layout of the reference's classes.  `_FlatOptimizer` holds what the three share.
 """
 import ctypes
-import weakref
 
 import torch
 
 from . import _lib
 from ._lib import check, ptr, stream_ptr
+from .models.mlp_autograd import flat_grad, flat_grad_reset
+from .models.nerf import NeRF
 
 
 class _FlatOptimizer(torch.optim.Optimizer):
@@ -37,10 +38,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self.flats = []
         for m in self.models:
             self.flats.append(torch.nn.Parameter(self._flatten(m), requires_grad=True))
-            # this optimizer announces every update (_bump_serial): weight images packed AHEAD of a step
-            # (RayStore.sample(pack_models=...)) may be trusted while the serial stands — and only while THIS optimizer is alive: the
-            # mark is a weak reference, so a model later stepped by another optimizer is not vouched for by a dead optimizer
-            m._serial_tracked = weakref.ref(self)
+            # this optimizer announces every update (NeRF.weights_changed): weight images packed AHEAD of a step
+            # (RayStore.sample(pack_models=...)) may be trusted while the serial stands — and only while THIS optimizer is alive.
+            # (A module that is not a NeRF — anything with flat_params() can be stepped — packs no images: nothing to announce.)
+            if isinstance(m, NeRF):
+                m.announced_by(self)
         super().__init__(self.flats, defaults)
         dev = self.flats[0].device
         if not self.flats[0].is_cuda:
@@ -106,7 +108,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _gather_grads(self):
         for m, flat in zip(self.models, self.flats):
             ps = m.flat_params()
-            fg = getattr(m, "_flat_grad", None)
+            fg = flat_grad(m)
             g0, g1 = ps[0].grad, ps[-1].grad
             if (fg is not None and g0 is not None and g1 is not None and g0.data_ptr() == fg.data_ptr()
                     and g1.data_ptr() + g1.numel() * 4 == fg.data_ptr() + fg.numel() * 4):
@@ -123,11 +125,6 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 flat.grad = g
             else:
                 flat.grad = None
-
-    def _bump_serial(self, idx):
-        """the weights of these models changed: packed weight images made before this point are stale (models/nerf.py)"""
-        for i in idx:
-            self.models[i]._weights_serial = getattr(self.models[i], "_weights_serial", 0) + 1
 
     # ---------------------------------------------------------------------------------------------- the update
     def _begin_step(self):
@@ -146,7 +143,9 @@ class _FlatOptimizer(torch.optim.Optimizer):
             raise _lib.NerfHipError("%s: the set of models with gradients changed between steps (%s -> %s); one shared step "
                                     "counter cannot represent that — use %s for partially frozen training"
                                     % (self._name, self._stepped, tuple(idx), self._elsewhere))
-        self._bump_serial(idx)
+        for i in idx:                                   # packed weight images made before this point are stale
+            if isinstance(self.models[i], NeRF):
+                self.models[i].weights_changed()
         return idx
 
     def _pointer_arrays(self, idx, *buffers):
@@ -160,7 +159,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def zero_grad(self, set_to_none=True):
         for m, flat in zip(self.models, self.flats):
             flat.grad = None
-            m._flat_grad = None
+            flat_grad_reset(m)
             for p in m.flat_params():
                 if set_to_none or p.grad is None:
                     p.grad = None
@@ -257,7 +256,8 @@ class FlatAdam(_FlatOptimizer):
 
     def applied_in_backward(self, models):
         self._applied = {id(m) for m in models}
-        self._bump_serial([j for j, mm in enumerate(self.models) if any(mm is m for m in models)])
+        for m in models:                                # (all of them this optimizer's: handle(models) found each)
+            m.weights_changed()
 
     # ---------------------------------------------------------------------------------------------- the update
     @torch.no_grad()

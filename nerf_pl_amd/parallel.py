@@ -19,6 +19,8 @@ import warnings
 import torch
 import torch.distributed as dist
 
+from .models.mlp_autograd import clear_grad_hooks, flat_grad, set_grad_hooks
+
 
 def shard_bounds(n, rank, world):
     """Contiguous [lo, hi) of `n` rays owned by `rank` (sizes differ by at most 1)."""
@@ -112,15 +114,11 @@ class GradSync:
 
     def attach(self):
         for m in self.models:
-            m._grad_ready_hook = self._on_grad_ready
-            m._grads_ready_hook = self._on_grads_ready if self.form == "merged" else None
+            set_grad_hooks(m, self._on_grad_ready, self._on_grads_ready if self.form == "merged" else None)
 
     def detach(self):
         for m in self.models:
-            if getattr(m, "_grad_ready_hook", None) == self._on_grad_ready:
-                m._grad_ready_hook = None
-            if getattr(m, "_grads_ready_hook", None) == self._on_grads_ready:
-                m._grads_ready_hook = None
+            clear_grad_hooks(m, self._on_grad_ready, self._on_grads_ready)
 
     def agree_any(self, flag):
         """True on every rank if `flag` is true on any (one small eager MAX all-reduce): ranks that must take the same branch —
@@ -220,7 +218,7 @@ class GradSync:
         for m in self.models:
             if id(m) in covered:
                 continue
-            flat = getattr(m, "_flat_grad", None)
+            flat = flat_grad(m)
             params = [p for p in m.parameters() if p.grad is not None]
             if flat is not None and params and self._aliases(params, flat) and id(m) not in issued_early:
                 direct.append(flat)                                      # issued below, together
@@ -247,7 +245,7 @@ class GradSync:
             return False
         for m, flat in rec.owners:
             params = [p for p in m.parameters() if p.grad is not None]
-            if not (any(m is x for x in self.models) and params and getattr(m, "_flat_grad", None) is flat
+            if not (any(m is x for x in self.models) and params and flat_grad(m) is flat
                     and self._aliases(params, flat)):
                 return False
         return True

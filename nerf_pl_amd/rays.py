@@ -8,6 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import check, device_guard, ptr, require_gpu, stream_ptr
+from .models.nerf import pack_ticket
 
 
 def get_ray_directions(H, W, focal, device="cuda"):
@@ -115,7 +116,7 @@ class RayStore:
         outs = D.draws(specs, dev, generator, batch=rb, pack=pack_models)
         batch = {"rays": rays, "rgbs": rgbs}
         if pack_models is not None:
-            batch["packed"] = (tuple(id(m) for m in pack_models[0]), pack_models[1], tuple(m._packed_serial for m in pack_models[0]))
+            batch["packed"] = pack_ticket(*pack_models)
         if return_ids:
             batch["ids"] = outs[0]
         if step_draws is not None:

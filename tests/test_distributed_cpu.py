@@ -13,6 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from nerf_pl_amd import parallel
+from nerf_pl_amd.models.mlp_autograd import flat_grad, grad_hooks, grads_ready
 
 
 def _free_port():
@@ -266,6 +267,8 @@ def _fused_backward_issue_order(check, rank, world):
         torch.manual_seed(3)
         coarse, fine = NeRF(), NeRF()
         gs = parallel.GradSync([coarse, fine], form=form)
+        for m_ in (coarse, fine):
+            m_.images_packed()                              # what the forward this backward belongs to did
         log = []
 
         def fake_multi(entries, dtype, adam=None, phases=7, workspace=None, g_scale=None):
@@ -284,7 +287,7 @@ def _fused_backward_issue_order(check, rank, world):
         ops.mlp_bwd_multi, dist.all_reduce = fake_multi, logging_ar
         try:
             ctx = SimpleNamespace(n_params=[24, 24], entries=[("fine", None, None, None), ("coarse", None, None, None)], dtype="bf16",
-                                  adam=None, models=[fine, coarse], serials=[0, 0])
+                                  adam=None, models=[fine, coarse], serials=[fine.pack_serial(), coarse.pack_serial()])
             grads = TS._TrainRender.backward(ctx, torch.ones(()))
             # autograd adopts the returned views as p.grad (parameter order of forward(): coarse, then fine)
             for p_, g_ in zip(coarse.flat_params() + fine.flat_params(), grads[3:]):
@@ -335,7 +338,7 @@ def _flat_and_alias(check, rank, world):
     m = _Tiny()
     flat = _base() * (rank + 1)
     _adopt(m, flat)
-    m._flat_grad = flat
+    grads_ready([m], [flat])                                # (no hook attached yet: records the buffer)
     parallel.GradSync([m]).sync()
     check("flat/averaged_in_place", torch.allclose(flat, _base() * (world + 1) / 2.0))
     # and the parameters' .grad still alias the averaged buffer
@@ -347,9 +350,8 @@ def _overlap(check, rank, world, m, gs):
     "the rest of backward" still runs) and sync() only waits and averages"""
     want = (world + 1) / 2.0
     flat = _base() * (rank + 1) + 1.0
-    m._flat_grad = flat
-    check("overlap/hook_attached", m._grad_ready_hook is not None)
-    m._grad_ready_hook(m, flat)                             # what models/mlp_autograd._param_grads does (p.grad still None)
+    check("overlap/hook_attached", grad_hooks([m])[0])
+    grads_ready([m], [flat])                                # what models/mlp_autograd._param_grads does (p.grad still None)
     _adopt(m, flat)
     started = gs.started_early
     gs.sync()
@@ -363,10 +365,10 @@ def _hooks_off(check, rank, world, m, gs):
     want = (world + 1) / 2.0
     gs.hooks_enabled = False
     _clear(m)
-    flat = m._flat_grad
+    flat = flat_grad(m)
     flat.copy_(_base() * (rank + 1))
     before = gs.started_early
-    m._grad_ready_hook(m, flat)
+    grads_ready([m], [flat])
     _adopt(m, flat)
     check("hooks_off/issues_nothing", gs.started_early == before == 1)
     gs.sync()
@@ -381,9 +383,8 @@ def _accumulation(check, rank, world, m, gs):
     for p in m.parameters():
         p.grad = torch.full_like(p, 10.0 * (rank + 1))
     flat = _base() * (rank + 1)
-    m._flat_grad = flat
     before = gs.started_early
-    m._grad_ready_hook(m, flat)
+    grads_ready([m], [flat])
     _accumulate(m, flat)
     gs.sync()
     check("accumulation/issues_nothing", gs.started_early == before)
@@ -395,12 +396,10 @@ def _two_backwards(check, rank, world, m, gs):
     want = (world + 1) / 2.0
     _clear(m)
     first = _base() * (rank + 1)
-    m._flat_grad = first
-    m._grad_ready_hook(m, first)
+    grads_ready([m], [first])
     _adopt(m, first)
     second = _base() * (rank + 1) * 2.0
-    m._flat_grad = second
-    m._grad_ready_hook(m, second)                           # waits for + finishes the first collective, issues nothing
+    grads_ready([m], [second])                              # waits for + finishes the first collective, issues nothing
     _accumulate(m, second)
     gs.sync()
     check("two_backwards/averaged", torch.allclose(_grads(m), _base() * want * 3.0))
@@ -410,8 +409,7 @@ def _copied_views_refused(check, rank, world, m, gs):
     """autograd COPIED the announced views instead of adopting them: refused, never silently un-averaged"""
     _clear(m)
     flat = _base() * (rank + 1)
-    m._flat_grad = flat
-    m._grad_ready_hook(m, flat)
+    grads_ready([m], [flat])
     _adopt(m, flat.clone())
     try:
         gs.sync()
@@ -427,7 +425,7 @@ def _two_models(rank):
         m = _Tiny()
         fl = _base() * (rank + 1) * (k + 1)
         _adopt(m, fl)
-        m._flat_grad = fl
+        grads_ready([m], [fl])
         ms.append(m)
         flats.append(fl)
     gs = parallel.GradSync(ms)
@@ -475,7 +473,7 @@ def _joint_models(rank, scale):
     flats = [joint[k * _N:(k + 1) * _N] for k in range(2)]
     for k, fl in enumerate(flats):
         fl.copy_(_base() * (rank + 1) * (k + 1) * scale)
-        ms[k]._flat_grad = fl
+        grads_ready([ms[k]], [fl])
     return ms, flats
 
 
@@ -488,9 +486,9 @@ def _joint(check, rank, world):
     ms, flats = _joint_models(rank, 1.0)
     gs = parallel.GradSync(ms)
     check("joint/hook/merged_is_default", gs.form == "merged")
-    check("joint/hook/one_hook_for_all_models", ms[0]._grads_ready_hook is not None and ms[0]._grads_ready_hook == ms[1]._grads_ready_hook)
+    check("joint/hook/one_hook_for_all_models", grad_hooks(ms)[1] is not None)
     with _patched("all_reduce", _counting) as sent:
-        ms[0]._grads_ready_hook(ms, flats)                  # what models/train_step._TrainRender.backward does (p.grad still None)
+        grads_ready(ms, flats)                              # what models/train_step._TrainRender.backward does (p.grad still None)
         check("joint/hook/one_message_over_joint_range", [t.numel() for t in sent] == [2 * _N])
         check("joint/hook/issue_log", gs.issue_log == [("joint", 2)])
         for m, fl in zip(ms, flats):
@@ -505,7 +503,7 @@ def _joint(check, rank, world):
     gs.hooks_enabled = False
     gs._coalesce_backends = ("nccl", "gloo")
     with _patched("all_reduce", _counting) as sent, _patched("_coalescing_manager", _counting) as entered:
-        ms[0]._grads_ready_hook(ms, flats)
+        grads_ready(ms, flats)
         for m, fl in zip(ms, flats):
             _adopt(m, fl)
         gs.sync()
@@ -530,7 +528,7 @@ def _joint(check, rank, world):
         for p in m.parameters():
             p.grad = torch.full_like(p, 10.0 * (rank + 1))
     with _patched("all_reduce", _counting) as sent:
-        ms[0]._grads_ready_hook(ms, flats)
+        grads_ready(ms, flats)
     check("joint/accumulation/issues_nothing", len(sent) == 0)
     for m, fl in zip(ms, flats):
         _accumulate(m, fl)

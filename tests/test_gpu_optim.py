@@ -261,7 +261,7 @@ def test_system_trains_with_radam_and_ranger(dev, name):
 
     def batches():
         for _ in range(20):
-            serials.append([getattr(m, "_weights_serial", 0) for m in system.models])
+            serials.append([m.weights_serial() for m in system.models])
             yield batch
     losses = [float(x) for x in fit(system, batches())]
     assert type(system.optimizer).__name__ == want

@@ -666,9 +666,34 @@ def test_pack_weights_train_equals_separate_packs(dev, dtype):
     m = m.to(dev)
     fwd = m.packed_weights(dtype).clone()
     bwd = m.packed_weights_bwd(dtype).clone()
-    m._packed_cache.pop(dtype), m._packed_cache.pop(("bwd", dtype))        # fresh (uninitialised) buffers
-    f2, b2 = m.packed_weights_train(dtype)
+    m2 = NeRF()                                                             # fresh (uninitialised) buffers: another model,
+    m2.load_state_dict(m.state_dict())                                      # the same weights
+    f2, b2 = m2.to(dev).packed_weights_train(dtype)
     assert torch.equal(fwd, f2) and torch.equal(bwd, b2)
+
+
+def test_backward_refuses_a_weight_image_repacked_from_updated_weights(dev):
+    """A training forward, an announced weight update of the fine model, a second training forward of the same models (it re-packs
+    the ONE W^T buffer per model from the updated weights): the first loss's backward raises instead of multiplying by the wrong
+    W^T; the second loss's backward runs.  8 rays x (8 + 8) samples, fp32, on the multi-launch forward (either form packs alike)."""
+    from nerf_pl_amd import ops
+    from nerf_pl_amd.models.train_step import render_rays_train
+    ms, emb = build_models([O.make_params(5, 4.0, 0.2), O.make_params(6, 4.0, 0.2)], dev, "fp32")
+    rays = O.make_rays(2, 8, "blender").to(dev)
+    tgt = torch.rand(8, 3, generator=torch.Generator().manual_seed(2)).to(dev)
+    prev = ops.set_render_fused(False)
+    try:
+        _, loss1, _ = render_rays_train(ms, emb, rays, tgt, 8, False, 0.0, 0.0, 8, True)
+        ms[1].weights_changed()
+        _, loss2, _ = render_rays_train(ms, emb, rays, tgt, 8, False, 0.0, 0.0, 8, True)
+        with pytest.raises(RuntimeError, match="re-packed from UPDATED weights by a later training forward"):
+            loss1.backward()
+        assert all(p.grad is None for m in ms for p in m.parameters())
+        loss2.backward()
+    finally:
+        ops.set_render_fused(prev)
+    torch.cuda.synchronize()
+    assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for m in ms for p in m.parameters())
 
 
 def test_loss_backward_scales_with_upstream_gradient(dev):

@@ -48,6 +48,7 @@ def _reference_grads(dev):
 def _reference_trajectory(dev, dtype):
     """STEPS steps of FlatAdam on the hand average: both ranks' gradients computed one after the other, averaged into the flat
     buffers the optimizer reads"""
+    from nerf_pl_amd.models.mlp_autograd import flat_grad
     from nerf_pl_amd.parallel import GradSync
     system = W.make_system(dev, dtype)
     (opt,), _ = system.configure_optimizers()
@@ -55,10 +56,10 @@ def _reference_trajectory(dev, dtype):
         gs = []
         for r in range(2):
             _plain_backward(system, W.make_batch(r, i, dev), i)
-            gs.append([m._flat_grad.clone() for m in system.models])
+            gs.append([flat_grad(m).clone() for m in system.models])
         for k, m in enumerate(system.models):
-            assert GradSync._aliases(list(m.parameters()), m._flat_grad)            # p.grad IS the buffer the average goes into
-            m._flat_grad.copy_((gs[0][k] + gs[1][k]) / 2)
+            assert GradSync._aliases(list(m.parameters()), flat_grad(m))            # p.grad IS the buffer the average goes into
+            flat_grad(m).copy_((gs[0][k] + gs[1][k]) / 2)
         opt.step()
     return W.train_state(system, opt)
 

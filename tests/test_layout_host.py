@@ -28,28 +28,26 @@ def test_dw_plan_header_is_plain_host_code(tmp_path):
 
 
 def test_ahead_of_step_weight_images_are_trusted_only_under_a_live_announcing_optimizer():
-    """`_serial_tracked` used to be a flag FlatAdam set and nobody cleared.  It is a weak reference to the optimizer now (a
-    model later stepped by something else is not vouched for by a dead FlatAdam), and load_state_dict — the reference's load_ckpt,
+    """the announcer's mark used to be a flag FlatAdam set and nobody cleared.  It is a weak reference to the optimizer now
+    (a model later stepped by something else is not vouched for by a dead FlatAdam), and load_state_dict — the reference's load_ckpt,
     utils/__init__.py:55-76 — bumps the weights' serial like an announced update."""
     import gc
-    import weakref
 
     from nerf_pl_amd.models import NeRF
-    from nerf_pl_amd.models.train_step import _tracked
 
     class Opt:                      # stands in for optim.FlatAdam (which needs a GPU): what matters is the weak reference
         pass
     m = NeRF()
-    assert not _tracked(m)
+    assert not m.announced()
     opt = Opt()
-    m._serial_tracked = weakref.ref(opt)
-    assert _tracked(m)
+    m.announced_by(opt)
+    assert m.announced()
     del opt
     gc.collect()
-    assert not _tracked(m)
-    before = getattr(m, "_weights_serial", 0)
+    assert not m.announced()
+    before = m.weights_serial()
     m.load_state_dict(NeRF().state_dict())
-    assert m._weights_serial == before + 1
+    assert m.weights_serial() == before + 1
 
 
 def _check_flat_layout(ops, gw, gb, flat):

@@ -123,6 +123,7 @@ def sc_agree(ctx):
 
 def _grad_case(form, overlap):
     def run(ctx):
+        from nerf_pl_amd.models.mlp_autograd import flat_grad
         from nerf_pl_amd.parallel import GradSync
         system = make_system(ctx.dev)
         (opt,), _ = system.configure_optimizers()
@@ -136,7 +137,7 @@ def _grad_case(form, overlap):
         sync.sync()
         res = flat_grads(system)
         res.update(issue_log=log, started_early=started, loss=float(out["loss"]),
-                   adopted=all(m._flat_grad is not None and GradSync._aliases(list(m.parameters()), m._flat_grad) for m in system.models))
+                   adopted=all(flat_grad(m) is not None and GradSync._aliases(list(m.parameters()), flat_grad(m)) for m in system.models))
         sync.detach()
         return res
     return run
