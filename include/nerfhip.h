@@ -680,6 +680,41 @@ int nerfhip_gif_quantize(const uint8_t* frames, int F, int H, int W, uint8_t* in
 int nerfhip_gif_lzw(const uint8_t* indices, int F, int H, int W, uint8_t* data, int32_t* lengths, void* workspace,
                     nerfhip_stream_t stream);
 
+/* ---- PNG encoder  (eval.py:138 `imageio.imwrite(os.path.join(dir_name, f'{i:03d}.png'), img_pred_)`) -----------
+ * The zlib data of an 8-bit grey / RGB / RGBA PNG as a pure function of the pixels (DESIGN.md §15 holds the definition,
+ * tests/png_ref.py restates it in numpy); the caller writes the container: signature, IHDR, one IDAT = 78 01 + data + the
+ * Adler-32 big-endian, IEND, and the chunk CRC-32s.  0 <= n <= 65535 images or streams; n == 0 is success and touches nothing;
+ * null pointers with n > 0 and sizes outside the ranges below are NERFHIP_E_BADARG before anything is launched.  Nothing is
+ * allocated, nothing synchronises.
+ *
+ * png_filter: images (n,H,W,C) uint8, C in {1, 3, 4}, H, W >= 1, H * (1 + W*C) < 2^31 -> streams (n, H * (1 + W*C)) uint8: per
+ * scanline the filter type and the filtered bytes.  All five filters (bpp = C, the row above row 0 is zeros) are formed from the
+ * raw neighbours; the one with the smallest sum of (v < 128 ? v : 256 - v) over its bytes is kept, a tie goes to the lowest type.
+ *
+ * png_deflate: streams (n, stream_bytes) uint8, 1 <= stream_bytes < 2^31 -> data (n, png_data_stride(stream_bytes)) uint8,
+ * lengths (n) int32, adler (n) uint32.  The stream is cut into strips of NERFHIP_PNG_STRIP bytes; each is one deflate block with
+ * dynamic Huffman codes (BFINAL on the last), the blocks follow each other bit by bit.  Tokens: a strip is cut into maximal runs
+ * of equal bytes; a run of L bytes is one literal, (L-1) / 258 matches of length 258 and distance 1, and for t = (L-1) % 258 one
+ * match of length t if t >= 3, else t literals.  Code lengths: png_code_lengths below.  Bytes behind lengths[i] are not written.
+ * lengths[i] == -1: a strip exceeded its derived worst case (a broken invariant, never input-dependent) or the data has 2^31
+ * bytes or more; that stream's data is not written.  png_data_stride is that worst case — per strip 17 + 57 + 287 * 14 bits of
+ * block header and 15 of end-of-block, 15 bits per byte — and 0 for a refused size.  `workspace` is 8-byte aligned
+ * (NERFHIP_E_ALIGN) and holds png_workspace_bytes(n, stream_bytes) bytes (0 for a refused size), about 15.9 KB per strip.
+ *
+ * png_code_lengths: HOST ONLY, no GPU call.  counts (n_symbols) uint32 -> lengths (n_symbols) uint8 with every length <= limit,
+ * 1 <= n_symbols <= 286, 1 <= limit <= 15, n_symbols <= 2^limit: the construction the strip kernel runs for its two alphabets
+ * (limit 15 and 7), from the same source (csrc/png_huff.h).  Used symbols in ascending (count, symbol) order; Huffman's merge
+ * of the two lightest, of equal weights a merged node before a leaf and the earlier before the later; depths above `limit`
+ * count as `limit`; while the Kraft sum exceeds 1, one code of the longest length below `limit` is lengthened by one and takes
+ * one code of length `limit` beside it; lengths go back longest first to the ascending order.  One used symbol: length 1.      */
+#define NERFHIP_PNG_STRIP 8192
+size_t nerfhip_png_workspace_bytes(int n, int64_t stream_bytes);
+size_t nerfhip_png_data_stride(int64_t stream_bytes);
+int nerfhip_png_filter(const uint8_t* images, int n, int H, int W, int C, uint8_t* streams, nerfhip_stream_t stream);
+int nerfhip_png_deflate(const uint8_t* streams, int n, int64_t stream_bytes, uint8_t* data, int32_t* lengths, uint32_t* adler,
+                        void* workspace, nerfhip_stream_t stream);
+int nerfhip_png_code_lengths(const uint32_t* counts, int n_symbols, int limit, uint8_t* lengths);
+
 #ifdef __cplusplus
 }
 #endif

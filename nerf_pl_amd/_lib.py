@@ -144,6 +144,11 @@ SIGNATURES = {
     "nerfhip_gif_data_stride": [_int, _int],
     "nerfhip_gif_quantize": [_c_void_p, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "nerfhip_gif_lzw": [_c_void_p, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_png_workspace_bytes": [_int, _i64],
+    "nerfhip_png_data_stride": [_i64],
+    "nerfhip_png_filter": [_c_void_p, _int, _int, _int, _int, _c_void_p, _c_void_p],
+    "nerfhip_png_deflate": [_c_void_p, _int, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_png_code_lengths": [_c_void_p, _int, _int, _c_void_p],
 }
 
 
@@ -191,7 +196,8 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_marching_cubes_workspace_bytes": ctypes.c_size_t, "nerfhip_mesh_cluster_workspace_bytes": ctypes.c_size_t,
              "nerfhip_jpeg_planes_bytes": ctypes.c_size_t, "nerfhip_ssim_workspace_bytes": ctypes.c_size_t,
              "nerfhip_depth_colormap_workspace_bytes": ctypes.c_size_t, "nerfhip_gif_workspace_bytes": ctypes.c_size_t,
-             "nerfhip_gif_data_stride": ctypes.c_size_t, "nerfhip_vol_workspace_bytes": ctypes.c_size_t}
+             "nerfhip_gif_data_stride": ctypes.c_size_t, "nerfhip_vol_workspace_bytes": ctypes.c_size_t,
+             "nerfhip_png_workspace_bytes": ctypes.c_size_t, "nerfhip_png_data_stride": ctypes.c_size_t}
 
 _lib = None
 

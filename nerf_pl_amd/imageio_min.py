@@ -3,7 +3,7 @@ PNG (8-bit RGB or grey, zlib-deflated, filter 0), PFM (datasets/depth_utils.py:4
 and the raw little-endian float32 dump of `--depth_format bytes` (eval.py:135-137); and the host half of scene loading
 (nerf_pl_amd/datasets): the PNG container parser, the JPEG marker parser and Pillow's Lanczos taps.  Host-side, numpy only —
 except the animated GIF of eval.py:145 at the end of the file, whose palettes and LZW data come from the GPU (csrc/gif.hip)
-and whose container is written here."""
+and whose container is written here, and the opt-in `png_bytes_device`, whose zlib data comes from the GPU (csrc/png.hip)."""
 import math
 import re
 import struct
@@ -101,6 +101,44 @@ def png_inflate(data):
     if len(raw) != h * (1 + w * ch):
         raise ValueError("PNG data holds %d bytes, %d x %d x %d needs %d" % (len(raw), h, w, ch, h * (1 + w * ch)))
     return w, h, ch, raw
+
+
+def png_bytes_device(images):
+    """(n, H, W) or (n, H, W, C) uint8 images ON THE DEVICE, C in (1, 3, 4) -> a list of n PNG file contents.
+    Filter choice, deflate (8192-byte strips, run-length matches, one dynamic-Huffman block each) and Adler-32 are formed on the
+    GPU (ops.png_filter, ops.png_deflate); one copy brings the data to the host and one the lengths and checksums; the
+    container and its chunk CRC-32s are written here."""
+    import torch
+
+    from . import ops
+    from ._lib import NerfHipError
+    if torch.is_tensor(images) and images.dim() == 3:
+        images = images.unsqueeze(3)
+    streams = ops.png_filter(images)
+    n, h, w, ch = images.shape
+    if n == 0:
+        return []
+    meta = torch.empty((2, n), device=images.device, dtype=torch.int32)
+    data, _, _ = ops.png_deflate(streams, meta=meta)
+    meta = meta.cpu().numpy()
+    lengths, adler = meta[0], meta[1]
+    if np.any(lengths < 0):
+        raise NerfHipError("png_deflate: a strip exceeded its worst-case size in image %d" % int(np.flatnonzero(lengths < 0)[0]))
+    data = data[:, :int(lengths.max())].cpu().numpy()
+    head = b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, {1: 0, 3: 2, 4: 6}[ch], 0, 0, 0))
+    tail = _chunk(b"IEND", b"")
+    return [head + _chunk(b"IDAT", b"\x78\x01" + data[i, :lengths[i]].tobytes() + struct.pack(">I", int(adler[i]) & 0xffffffff)) + tail
+            for i in range(n)]
+
+
+def write_png_device(paths, images):
+    """One file per image of `png_bytes_device(images)`: `paths` is a list of n names."""
+    files = png_bytes_device(images)
+    if len(paths) != len(files):
+        raise ValueError("write_png_device: %d paths for %d images" % (len(paths), len(files)))
+    for path, data in zip(paths, files):
+        with open(path, "wb") as f:
+            f.write(data)
 
 
 # zigzag position -> natural (row-major) index of an 8 x 8 block

@@ -196,7 +196,8 @@ def image_to_u8(rgb):
 
 
 @torch.no_grad()
-def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="pfm", window_size=3, gif_path=None, fps=30):
+def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="pfm", window_size=3, gif_path=None, fps=30,
+             png_encoder="host"):
     """The loop of the reference's eval.py (eval.py:112-149) with its tail on the GPU.
 
     dataset: `len`, `img_wh` = (w, h), items with 'rays' (h*w, 8) and optionally 'rgbs' (h*w, 3).  renderer: rays on the GPU ->
@@ -209,6 +210,10 @@ def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="p
     `imageio.mimsave(gif_path, imgs, fps=fps)` of eval.py:145 is.  A batch holds per frame 3 bytes per pixel of frames, 1 of
     indices, about 1.5 of worst-case data and 38.5 KB per 3838 pixels of strip workspace — about 10 MB at 800 x 800, 81 MB per
     batch.  With `gif_path=None` nothing of this runs: the returned dict and the files written are what they were.
+    `png_encoder`: "host" (the default) writes `{i:03d}.png` with `imageio_min.write_png` (filter 0, zlib on the host); "gpu"
+    encodes the uint8 image where it already is (`imageio_min.write_png_device`, DESIGN.md §15: adaptive filters, strip
+    deflate and Adler-32 on the device) under the same name — the same pixels in a different, smaller file.  Anything else is
+    a ValueError.
 
     Returns {'psnr': [...], 'ssim': [...], 'mean_psnr', 'mean_ssim', 'images': [(h, w, 3) uint8 arrays]} (the lists are empty
     and the means None for a dataset without ground truth)."""
@@ -217,7 +222,9 @@ def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="p
     import numpy as np
 
     from . import metrics
-    from .imageio_min import GIF_BATCH, GifWriter, depth_bytes, save_pfm, write_png
+    from .imageio_min import GIF_BATCH, GifWriter, depth_bytes, save_pfm, write_png, write_png_device
+    if png_encoder not in ("host", "gpu"):
+        raise ValueError("png_encoder must be 'host' or 'gpu', got %r" % (png_encoder,))
     w, h = dataset.img_wh
     if dir_name is not None:
         os.makedirs(dir_name, exist_ok=True)
@@ -250,7 +257,10 @@ def evaluate(dataset, renderer, dir_name=None, save_depth=False, depth_format="p
             else:
                 with open(os.path.join(dir_name, "depth_%03d" % i), "wb") as f:
                     f.write(depth_bytes(depth))
-        write_png(os.path.join(dir_name, "%03d.png" % i), img)
+        if png_encoder == "gpu":
+            write_png_device([os.path.join(dir_name, "%03d.png" % i)], img_dev.unsqueeze(0))
+        else:
+            write_png(os.path.join(dir_name, "%03d.png" % i), img)
     if gif is not None and images:
         if pending:
             gif.append(torch.stack(pending))

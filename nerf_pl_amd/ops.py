@@ -1145,6 +1145,63 @@ def gif_lzw(indices, H, W, workspace=None):
     return data, lengths
 
 
+# ------------------------------------------------------------------------------- PNG encoder (eval.py:138)
+PNG_STRIP = 8192            # NERFHIP_PNG_STRIP
+
+
+def png_workspace(n, stream_bytes, device):
+    """The scratch buffer png_deflate takes (about 15.9 KB per 8192-byte strip)."""
+    nbytes = _lib.load().nerfhip_png_workspace_bytes(n, stream_bytes)
+    if n > 0 and nbytes == 0:
+        raise NerfHipError("png: %d streams of %d bytes are refused (1..2^31 - 1 bytes, at most 65535 streams)" % (n, stream_bytes))
+    return torch.empty(max(1, nbytes // 8), device=device, dtype=torch.int64)
+
+
+@device_guard
+def png_filter(images):
+    """nerfhip_png_filter: images (n, H, W, C) uint8 on the device, C in (1, 3, 4) -> streams (n, H * (1 + W*C)) uint8: every
+    scanline behind the type of the filter with the smallest absolute sum.  No host synchronisation."""
+    images = _require_u8("png_filter: images", images)
+    if images.dim() != 4 or images.shape[3] not in (1, 3, 4) or images.shape[1] < 1 or images.shape[2] < 1:
+        raise NerfHipError("png_filter: expected (n, H, W, C) with H, W >= 1 and C in (1, 3, 4), got %s" % (tuple(images.shape),))
+    n, H, W, C = images.shape
+    if H * (1 + W * C) >= 2 ** 31 or n > 65535:
+        raise NerfHipError("png_filter: %d images of %d x %d x %d are refused (H * (1 + W*C) < 2^31, n <= 65535)" % (n, H, W, C))
+    streams = torch.empty((n, H * (1 + W * C)), device=images.device, dtype=torch.uint8)
+    check(_lib.load().nerfhip_png_filter(ptr(images), n, H, W, C, ptr(streams), stream_ptr()), "nerfhip_png_filter")
+    return streams
+
+
+@device_guard
+def png_deflate(streams, workspace=None, meta=None):
+    """nerfhip_png_deflate: streams (n, stream_bytes) uint8 on the device -> (data (n, stride) uint8, lengths (n,) int32,
+    adler (n,) int32).  Per stream the raw deflate data (strips of PNG_STRIP bytes, one dynamic-Huffman block each), its length
+    in bytes and the stream's Adler-32 — the 32 bits of the unsigned sum in an int32 (`& 0xffffffff` on the host); the bytes
+    behind a length are undefined.  lengths and adler are rows 0 and 1 of `meta`, a (2, n) int32 device tensor (allocated when
+    not given), so that one copy brings both to the host.  No host synchronisation: a length of -1 (a strip exceeded its worst
+    case) is for the caller to check when it reads the lengths (imageio_min.png_bytes_device does)."""
+    streams = _require_u8("png_deflate: streams", streams)
+    if streams.dim() != 2 or streams.shape[1] < 1:
+        raise NerfHipError("png_deflate: expected (n, stream_bytes >= 1), got %s" % (tuple(streams.shape),))
+    n, nbytes = streams.shape
+    dev = streams.device
+    lib = _lib.load()
+    ws = workspace if workspace is not None else png_workspace(n, nbytes, dev)
+    if not torch.is_tensor(ws) or ws.device != dev or ws.numel() * ws.element_size() < lib.nerfhip_png_workspace_bytes(n, nbytes):
+        raise NerfHipError("png_deflate: the workspace must be a tensor on %s of png_workspace(%d, %d)'s size" % (dev, n, nbytes))
+    stride = lib.nerfhip_png_data_stride(nbytes)
+    if meta is None:
+        meta = torch.empty((2, n), device=dev, dtype=torch.int32)
+    elif not torch.is_tensor(meta) or meta.device != dev or meta.dtype != torch.int32 or tuple(meta.shape) != (2, n) \
+            or not meta.is_contiguous():
+        raise NerfHipError("png_deflate: meta must be a contiguous (2, %d) int32 tensor on %s" % (n, dev))
+    data = torch.empty((n, stride), device=dev, dtype=torch.uint8)
+    lengths, adler = meta[0], meta[1]
+    check(lib.nerfhip_png_deflate(ptr(streams), n, nbytes, ptr(data), ptr(lengths), ptr(adler), ptr(ws), stream_ptr()),
+          "nerfhip_png_deflate")
+    return data, lengths, adler
+
+
 # ------------------------------------------------------------------------------- scene loading (datasets/blender.py:47-58, 90-95)
 def _require_u8(name, t):
     if not torch.is_tensor(t):
