@@ -1,13 +1,15 @@
 // The animated GIF of the reference's eval loop (eval.py:145 `imageio.mimsave`) formed on the device: per frame a 256-colour
 // median cut over a 32 x 32 x 32 histogram, the index image and its palette, and the LZW code stream cut into strips that each
 // start with a clear code, so that every strip is encoded by its own lane.  The exact integer definition, the strip length and
-// the byte layout of the result: DESIGN.md §13 and include/nerfhip.h.  The host writes the container around the data.
+// the byte layout of the result: DESIGN.md §13 and include/nerfhip.h.  The host writes the container around the data.  The bit
+// writer, the scan of the strips' bit lengths and the gather of the bytes are the ones png.hip has: strip_bits.h, block_scan.h.
 #include "block_scan.h"
 #include "common.h"
+#include "strip_bits.h"
 
 namespace {
 
-using nerfhip::block_excl_scan;
+using nerfhip::carve;
 
 constexpr int kBlock = 256;              // threads of the per-pixel and per-byte kernels
 constexpr int kRun = 16;                 // consecutive pixels per thread of the per-pixel kernels
@@ -23,7 +25,6 @@ static_assert(257 + kStrip <= 4095, "a strip must never fill the code table");
 static_assert((kStrip + 2) * 12 <= kStripWords * 32, "strip bit buffer too small");
 static_assert(2 * (kStrip - 1) < kTable, "hash load must stay under one half");
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ __device__ inline int64_t strips_of(int64_t hw) { return (hw + kStrip - 1) / kStrip; }
 
 struct GifWs {
@@ -41,14 +42,14 @@ __host__ __device__ inline GifWs gif_ws(void* base, int64_t F, int64_t hw, size_
     const int64_t S = strips_of(hw);
     char* p = (char*)base;
     GifWs w;
-    w.hist = (uint32_t*)p; p += align256((size_t)F * kBins * 4);
-    w.sums = (unsigned long long*)p; p += align256((size_t)F * 256 * 4 * 8);
-    w.lut = (unsigned char*)p; p += align256((size_t)F * kBins);
-    w.bitlen = (int32_t*)p; p += align256((size_t)F * S * 4);
-    w.off = (int64_t*)p; p += align256((size_t)F * S * 8);
-    w.total = (int64_t*)p; p += align256((size_t)F * 8);
-    w.table = (uint32_t*)p; p += align256((size_t)F * S * kTable * 4);
-    w.bits = (uint32_t*)p; p += align256((size_t)F * S * kStripWords * 4);
+    w.hist = carve<uint32_t>(p, (size_t)F * kBins);
+    w.sums = carve<unsigned long long>(p, (size_t)F * 256 * 4);
+    w.lut = carve<unsigned char>(p, (size_t)F * kBins);
+    w.bitlen = carve<int32_t>(p, (size_t)F * S);
+    w.off = carve<int64_t>(p, (size_t)F * S);
+    w.total = carve<int64_t>(p, (size_t)F);
+    w.table = carve<uint32_t>(p, (size_t)F * S * kTable);
+    w.bits = carve<uint32_t>(p, (size_t)F * S * kStripWords);
     if (bytes) *bytes = (size_t)(p - (char*)base);
     return w;
 }
@@ -265,21 +266,6 @@ __global__ void __launch_bounds__(kBlock) gif_palette(GifWs w, unsigned char* __
 }
 
 // ---- LZW ---------------------------------------------------------------------------------------------------------------------
-struct BitSink {
-    uint32_t* words;
-    unsigned long long acc;
-    int nacc, nwords;
-    __device__ __forceinline__ void put(int code, int width) {
-        acc |= (unsigned long long)code << nacc;
-        nacc += width;
-        if (nacc >= 32) {
-            words[nwords++] = (uint32_t)acc;
-            acc >>= 32;
-            nacc -= 32;
-        }
-    }
-};
-
 // One strip per lane.  The dictionary is an open-addressing hash over (prefix << 8 | byte) in the strip's own kTable slots; a
 // strip adds at most kStrip - 1 entries, so a free slot always exists, and the explicit probe bound only turns a broken
 // invariant into bitlen = -1 instead of a spin.  The strip's last emission is the clear code of the next strip (the end code
@@ -293,7 +279,8 @@ __global__ void __launch_bounds__(64) gif_strips(const unsigned char* __restrict
     const int count = (int)(hw - start < kStrip ? hw - start : kStrip);
     const unsigned char* in = indices + f * hw + start;
     uint32_t* table = w.table + g * kTable;
-    BitSink out = {w.bits + g * kStripWords, 0ull, 0, 0};
+    nerfhip::BitWriter<nerfhip::StoreWord> out;      // the strip's words are this lane's alone
+    out.start(w.bits + g * kStripWords, 0);
     int next = 258, width = 9;
     if (s == 0) out.put(256, 9);
     int prefix = in[0];
@@ -326,8 +313,8 @@ __global__ void __launch_bounds__(64) gif_strips(const unsigned char* __restrict
     ++next;                                   // the decoder assigns a code for this emission too
     if (next > (1 << width)) ++width;
     out.put(s + 1 == S ? 257 : 256, width);
-    if (out.nacc > 0) out.words[out.nwords] = (uint32_t)out.acc;
-    w.bitlen[g] = out.nwords * 32 + out.nacc;
+    out.finish();
+    w.bitlen[g] = out.bits();
 }
 
 // One workgroup per frame: exclusive scan of the strips' bit lengths, the frame's total and the length of its sub-blocked data.
@@ -336,27 +323,18 @@ __global__ void __launch_bounds__(kCutBlock) gif_scan(int64_t S, GifWs w, int32_
     const int64_t f = blockIdx.x;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
-    int64_t carry = 0;
-    for (int64_t base = 0; base < S; base += kCutBlock) {
-        const int64_t i = base + threadIdx.x;
-        const int32_t len = i < S ? w.bitlen[f * S + i] : 0;
-        if (len < 0) atomicOr(&bad, 1);
-        int64_t tot;
-        const int64_t ex = block_excl_scan<kCutBlock>((int64_t)(len < 0 ? 0 : len), tot);
-        if (i < S) w.off[f * S + i] = carry + ex;
-        carry += tot;
-    }
+    const int64_t bits = nerfhip::block_offsets_scan<kCutBlock>(
+        S, w.off + f * S, [&](int64_t i) { return nerfhip::strip_bits_or_flag(w.bitlen[f * S + i], &bad); });
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int64_t n = (carry + 7) / 8;
-        w.total[f] = carry;
+        const int64_t n = (bits + 7) / 8;
+        w.total[f] = bits;
         lengths[f] = bad ? -1 : (int32_t)(n + (n + 254) / 255);
     }
 }
 
-// Gather: one thread per byte of the frame's sub-blocked data.  A length byte stands at every 256th position; a data byte finds
-// the strip that holds its first bit by binary search over the offsets and collects its 8 bits from that strip and the next
-// ones.  No byte has two writers.
+// Gather: one thread per byte of the frame's sub-blocked data.  A length byte stands at every 256th position; a data byte is
+// gather_byte (strip_bits.h) of its position in the frame's stream.  No byte has two writers.
 __global__ void __launch_bounds__(kBlock) gif_gather(int64_t S, int64_t stride, GifWs w, const int32_t* __restrict__ lengths,
                                                      unsigned char* __restrict__ data) {
     const int64_t f = blockIdx.y;
@@ -368,30 +346,8 @@ __global__ void __launch_bounds__(kBlock) gif_gather(int64_t S, int64_t stride, 
         const int64_t left = n - 255 * (p >> 8);
         v = left < 255 ? (unsigned)left : 255u;
     } else {
-        const int64_t* off = w.off + f * S;
-        const int32_t* len = w.bitlen + f * S;
-        int64_t bit = 8 * (255 * (p >> 8) + (p & 255) - 1);
-        int64_t lo = 0, hi = S - 1;                 // the last strip whose offset is <= bit
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (off[mid] <= bit) lo = mid; else hi = mid - 1;
-        }
-        int64_t s = lo;
-        int got = 0;
-        v = 0;
-        while (got < 8 && s < S) {
-            const int64_t q = bit - off[s];
-            const int avail = (int)(len[s] - q);
-            if (avail <= 0) { ++s; continue; }
-            const int take = avail < 8 - got ? avail : 8 - got;
-            const uint32_t* words = w.bits + (f * S + s) * kStripWords;
-            const int word = (int)(q >> 5), sh = (int)(q & 31);
-            unsigned long long x = words[word];
-            if (sh + take > 32) x |= (unsigned long long)words[word + 1] << 32;
-            v |= (unsigned)((x >> sh) & ((1u << take) - 1u)) << got;
-            got += take;
-            bit += take;
-        }
+        const int64_t bit = 8 * (255 * (p >> 8) + (p & 255) - 1);
+        v = nerfhip::gather_byte(w.off + f * S, w.bitlen + f * S, w.bits, f * S, S, kStripWords, bit);
     }
     data[f * stride + p] = (unsigned char)v;
 }

@@ -1,6 +1,7 @@
 // Mesh extraction from a sigma grid (extract_color_mesh.py:144-285): marching cubes, largest-cluster cleanup, vertex normals
 // and per-view colour fusion.  Every kernel is one thread per lattice point / triangle / vertex; the only cross-block
-// communication is the block-total scan (one workgroup) between two launches.  Layouts and byte counts: DESIGN.md, mesh.
+// communication is the block-total scan (one workgroup, block_scan.h's offsets scan) between two launches.  Layouts and byte
+// counts: DESIGN.md, mesh.
 #include "block_scan.h"
 #include "common.h"
 #include "mc_tables.h"
@@ -8,6 +9,7 @@
 namespace {
 
 using nerfhip::block_excl_scan;
+using nerfhip::carve;
 
 constexpr int kBlock = 256;        // threads of every per-element kernel here (4 waves)
 constexpr int kScanBlock = 1024;   // the single workgroup that scans the block totals
@@ -36,25 +38,19 @@ struct McWs {
     int64_t* off_t;
 };
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-__host__ __device__ inline McWs mc_ws(void* base, int64_t npts) {
+__host__ __device__ inline McWs mc_ws(void* base, int64_t npts, size_t* bytes) {
     const int64_t nb = (npts + kBlock - 1) / kBlock;
     char* p = (char*)base;
     McWs w;
-    w.mask = (unsigned char*)p; p += align256(npts);
-    w.cube = (unsigned char*)p; p += align256(npts);
-    w.vbase = (int32_t*)p; p += align256(4 * npts);
-    w.blk_v = (int32_t*)p; p += align256(4 * nb);
-    w.blk_t = (int32_t*)p; p += align256(4 * nb);
-    w.off_v = (int64_t*)p; p += align256(8 * nb);
-    w.off_t = (int64_t*)p; p += align256(8 * nb);
+    w.mask = carve<unsigned char>(p, npts);
+    w.cube = carve<unsigned char>(p, npts);
+    w.vbase = carve<int32_t>(p, npts);
+    w.blk_v = carve<int32_t>(p, nb);
+    w.blk_t = carve<int32_t>(p, nb);
+    w.off_v = carve<int64_t>(p, nb);
+    w.off_t = carve<int64_t>(p, nb);
+    if (bytes) *bytes = (size_t)(p - (char*)base);
     return w;
-}
-
-size_t mc_ws_bytes(int64_t npts) {
-    const int64_t nb = (npts + kBlock - 1) / kBlock;
-    return 2 * align256(npts) + align256(4 * npts) + 2 * align256(4 * nb) + 2 * align256(8 * nb);
 }
 
 // Pass 1: per point its crossed-edge mask and cube case; per block the vertex and triangle totals.
@@ -98,18 +94,8 @@ __global__ void __launch_bounds__(kScanBlock) scan_totals(const int32_t* __restr
                                                           int64_t* __restrict__ totals) {
     for (int which = 0; which < 2; ++which) {
         const int32_t* in = which ? b : a;
-        int64_t* out = which ? off_b : off_a;
-        const int64_t n = which ? nb : na;
-        int64_t carry = 0;
-        for (int64_t base = 0; base < n; base += kScanBlock) {
-            const int64_t i = base + threadIdx.x;
-            const int64_t v = i < n ? (int64_t)in[i] : 0;
-            int64_t tot;
-            const int64_t ex = block_excl_scan<kScanBlock>(v, tot);
-            if (i < n) out[i] = carry + ex;
-            carry += tot;
-        }
-        if (threadIdx.x == 0) totals[which] = carry;
+        const int64_t sum = nerfhip::block_offsets_scan<kScanBlock>(which ? nb : na, which ? off_b : off_a, [&](int64_t i) { return in[i]; });
+        if (threadIdx.x == 0) totals[which] = sum;
     }
 }
 
@@ -183,29 +169,24 @@ struct ClWs {
     unsigned long long* status;   // nonzero: a union gave up after its retry bound
 };
 
-__host__ __device__ inline ClWs cl_ws(void* base, int64_t V, int64_t T) {
+__host__ __device__ inline ClWs cl_ws(void* base, int64_t V, int64_t T, size_t* bytes) {
     const int64_t bt = (T + kBlock - 1) / kBlock, bv = (V + kBlock - 1) / kBlock;
     char* p = (char*)base;
     ClWs w;
-    w.parent = (int32_t*)p; p += align256(4 * T);
-    w.label = (int32_t*)p; p += align256(4 * T);
-    w.count = (int32_t*)p; p += align256(4 * T);
-    w.tflag = (unsigned char*)p; p += align256(T);
-    w.vflag = (unsigned char*)p; p += align256(V);
-    w.vnew = (int32_t*)p; p += align256(4 * V);
-    w.blk_t = (int32_t*)p; p += align256(4 * bt);
-    w.blk_v = (int32_t*)p; p += align256(4 * bv);
-    w.off_t = (int64_t*)p; p += align256(8 * bt);
-    w.off_v = (int64_t*)p; p += align256(8 * bv);
-    w.best = (uint64_t*)p; p += 256;
-    w.status = (unsigned long long*)p; p += 256;
+    w.parent = carve<int32_t>(p, T);
+    w.label = carve<int32_t>(p, T);
+    w.count = carve<int32_t>(p, T);
+    w.tflag = carve<unsigned char>(p, T);
+    w.vflag = carve<unsigned char>(p, V);
+    w.vnew = carve<int32_t>(p, V);
+    w.blk_t = carve<int32_t>(p, bt);
+    w.blk_v = carve<int32_t>(p, bv);
+    w.off_t = carve<int64_t>(p, bt);
+    w.off_v = carve<int64_t>(p, bv);
+    w.best = carve<uint64_t>(p, 1);
+    w.status = carve<unsigned long long>(p, 1);
+    if (bytes) *bytes = (size_t)(p - (char*)base);
     return w;
-}
-
-size_t cl_ws_bytes(int64_t V, int64_t T) {
-    const int64_t bt = (T + kBlock - 1) / kBlock, bv = (V + kBlock - 1) / kBlock;
-    return 3 * align256(4 * T) + align256(T) + align256(V) + align256(4 * V) + align256(4 * bt) + align256(4 * bv) +
-           align256(8 * bt) + align256(8 * bv) + 512;
 }
 
 __device__ __forceinline__ int ld_relaxed(const int32_t* p) {
@@ -477,14 +458,16 @@ inline bool mc_dims_ok(int64_t n0, int64_t n1, int64_t n2) {
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------
 extern "C" size_t nerfhip_marching_cubes_workspace_bytes(int64_t n0, int64_t n1, int64_t n2) {
     if (!mc_dims_ok(n0, n1, n2)) return 0;
-    return mc_ws_bytes(n0 * n1 * n2);
+    size_t bytes = 0;
+    mc_ws(nullptr, n0 * n1 * n2, &bytes);
+    return bytes;
 }
 
 extern "C" int nerfhip_marching_cubes_count(const float* volume, int64_t n0, int64_t n1, int64_t n2, double iso, void* workspace,
                                             int64_t* totals, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(volume && workspace && totals && mc_dims_ok(n0, n1, n2));
     const int64_t npts = n0 * n1 * n2;
-    const McWs w = mc_ws(workspace, npts);
+    const McWs w = mc_ws(workspace, npts, nullptr);
     const unsigned nb = blocks(npts);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(mc_count, dim3(nb), dim3(kBlock), 0, s, volume, (int)n0, (int)n1, (int)n2, iso, w);
@@ -496,7 +479,7 @@ extern "C" int nerfhip_marching_cubes_emit(const float* volume, int64_t n0, int6
                                            const int64_t* totals, double* vertices, int32_t* triangles, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(volume && workspace && totals && vertices && triangles && mc_dims_ok(n0, n1, n2));
     const int64_t npts = n0 * n1 * n2;
-    const McWs w = mc_ws(workspace, npts);
+    const McWs w = mc_ws(workspace, npts, nullptr);
     const unsigned nb = blocks(npts);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(mc_emit_vertices, dim3(nb), dim3(kBlock), 0, s, volume, (int)n0, (int)n1, (int)n2, iso, w, totals, vertices);
@@ -512,14 +495,16 @@ extern "C" int nerfhip_mesh_edge_keys(const int32_t* triangles, int64_t T, int64
 
 extern "C" size_t nerfhip_mesh_cluster_workspace_bytes(int64_t V, int64_t T) {
     if (V <= 0 || T <= 0 || V > INT32_MAX || T > INT32_MAX / 3) return 0;
-    return cl_ws_bytes(V, T);
+    size_t bytes = 0;
+    cl_ws(nullptr, V, T, &bytes);
+    return bytes;
 }
 
 extern "C" int nerfhip_mesh_largest_cluster(const int32_t* triangles, int64_t V, int64_t T, const int64_t* sorted_keys,
                                             const int64_t* order, void* workspace, int64_t* totals, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(triangles && sorted_keys && order && workspace && totals && V > 0 && T > 0 && V <= INT32_MAX &&
                       T <= INT32_MAX / 3);
-    const ClWs w = cl_ws(workspace, V, T);
+    const ClWs w = cl_ws(workspace, V, T, nullptr);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cl_init, dim3(blocks(V > T ? V : T)), dim3(kBlock), 0, s, V, T, w);
     if (T > 1) hipLaunchKernelGGL(cl_union, dim3(blocks(3 * T - 1)), dim3(kBlock), 0, s, sorted_keys, order, 3 * T, w);
@@ -538,7 +523,7 @@ extern "C" int nerfhip_mesh_cluster_compact(const int32_t* triangles, int64_t V,
                                             int32_t* kept_triangles, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(triangles && workspace && kept_vertex_ids && kept_triangles && V > 0 && T > 0 && V <= INT32_MAX &&
                       T <= INT32_MAX / 3);
-    const ClWs w = cl_ws(workspace, V, T);
+    const ClWs w = cl_ws(workspace, V, T, nullptr);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(cl_compact_vertices, dim3(blocks(V)), dim3(kBlock), 0, s, V, w, kept_vertex_ids);
     hipLaunchKernelGGL(cl_compact_triangles, dim3(blocks(T)), dim3(kBlock), 0, s, triangles, T, w, kept_triangles);

@@ -2,15 +2,19 @@
 // the filter of the smallest absolute sum, the filtered stream cut into strips that each become one dynamic-Huffman deflate
 // block of literals and distance-1 matches, and the stream's Adler-32.  The exact definition, the strip length and the byte
 // layout of the result: DESIGN.md §15 and include/nerfhip.h; tests/png_ref.py restates it in numpy.  The host writes the
-// container (signature, chunks, CRC-32) around the data.
+// container (signature, chunks, CRC-32) around the data.  The bit writer, the scan of the strips' bit lengths and the gather of
+// the bytes are the ones gif.hip has: strip_bits.h, block_scan.h.
 #include "block_scan.h"
 #include "common.h"
 #include "png_huff.h"
+#include "strip_bits.h"
 
 namespace {
 
 using nerfhip::block_excl_scan;
+using nerfhip::carve;
 using nerfhip::HuffScratch;
+using StripBits = nerfhip::BitWriter<nerfhip::OrWord>;      // into the strip's zeroed words in LDS, several threads at once
 
 constexpr int kBlock = 256;                       // threads of the filter, strip and gather kernels
 constexpr int kScanBlock = 1024;                  // the one workgroup per stream that scans strip lengths
@@ -32,7 +36,6 @@ static_assert((uint64_t)255 * kStrip * kChunk < ((uint64_t)1 << 32), "a thread's
 
 __constant__ unsigned char kClOrder[kCl] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ __device__ inline int64_t strips_of(int64_t bytes) { return (bytes + kStrip - 1) / kStrip; }
 
 struct PngWs {
@@ -48,12 +51,12 @@ __host__ __device__ inline PngWs png_ws(void* base, int64_t n, int64_t bytes, si
     const int64_t S = strips_of(bytes);
     char* p = (char*)base;
     PngWs w;
-    w.bitlen = (int32_t*)p; p += align256((size_t)n * S * 4);
-    w.off = (int64_t*)p; p += align256((size_t)n * S * 8);
-    w.total = (int64_t*)p; p += align256((size_t)n * 8);
-    w.sum_a = (uint32_t*)p; p += align256((size_t)n * S * 4);
-    w.sum_b = (uint32_t*)p; p += align256((size_t)n * S * 4);
-    w.bits = (uint32_t*)p; p += align256((size_t)n * S * kStripWords * 4);
+    w.bitlen = carve<int32_t>(p, (size_t)n * S);
+    w.off = carve<int64_t>(p, (size_t)n * S);
+    w.total = carve<int64_t>(p, (size_t)n);
+    w.sum_a = carve<uint32_t>(p, (size_t)n * S);
+    w.sum_b = carve<uint32_t>(p, (size_t)n * S);
+    w.bits = carve<uint32_t>(p, (size_t)n * S * kStripWords);
     if (size) *size = (size_t)(p - (char*)base);
     return w;
 }
@@ -116,30 +119,6 @@ __global__ void __launch_bounds__(kBlock) png_filter_rows(const unsigned char* _
 }
 
 // ---- deflate -----------------------------------------------------------------------------------------------------------------
-struct LdsBits {                       // bits into shared words: OR only, so the order of the writers does not matter
-    uint32_t* words;
-    unsigned long long acc;
-    int nacc, w;
-    __device__ __forceinline__ void start(uint32_t* base, int bit) {
-        words = base;
-        acc = 0;
-        nacc = bit & 31;
-        w = bit >> 5;
-    }
-    __device__ __forceinline__ void put(uint32_t v, int nb) {      // nb <= 21
-        acc |= (unsigned long long)v << nacc;
-        nacc += nb;
-        if (nacc >= 32) {
-            atomicOr(&words[w++], (uint32_t)acc);
-            acc >>= 32;
-            nacc -= 32;
-        }
-    }
-    __device__ __forceinline__ void finish() {
-        if (nacc > 0) atomicOr(&words[w], (uint32_t)acc);
-    }
-};
-
 struct StripState {
     unsigned char bytes[kStrip];
     uint32_t bits[kStripWords];
@@ -321,7 +300,7 @@ __global__ void __launch_bounds__(kBlock) png_strip(const unsigned char* __restr
                 if (pass) st.code[i] = (uint16_t)c; else st.cl_code[i] = (unsigned char)c;
             }
         }
-        LdsBits out;
+        StripBits out;
         out.start(st.bits, 0);
         out.put(s + 1 == S ? 1u : 0u, 1);
         out.put(2, 2);
@@ -333,7 +312,7 @@ __global__ void __launch_bounds__(kBlock) png_strip(const unsigned char* __restr
             out.put((uint32_t)st.cl_code[sym] | (uint32_t)ev << st.cl_len[sym], st.cl_len[sym] + eb);
         });
         out.finish();
-        st.head_bits = out.w * 32 + out.nacc;
+        st.head_bits = out.bits();
     }
     __syncthreads();
 
@@ -343,7 +322,7 @@ __global__ void __launch_bounds__(kBlock) png_strip(const unsigned char* __restr
     const int before = block_excl_scan<kBlock>(mine, tokens);
     const int total = st.head_bits + tokens + st.len[256];
     if (total <= kStripBits) {                             // (always: kStripBits is the derived worst case)
-        LdsBits out;
+        StripBits out;
         out.start(st.bits, st.head_bits + before);
         for_tokens(st.bytes, c0, c1, start, next, [&](int sym, int eb, int ev) {
             const int l = st.len[sym];
@@ -378,70 +357,39 @@ __global__ void __launch_bounds__(kScanBlock) png_scan(int64_t stream_bytes, int
     const int64_t f = blockIdx.x;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
-    int64_t carry = 0;
     unsigned long long sa = 0, sb = 0;
-    for (int64_t base = 0; base < S; base += kScanBlock) {
-        const int64_t i = base + threadIdx.x;
-        const int32_t len = i < S ? w.bitlen[f * S + i] : 0;
-        if (len < 0) atomicOr(&bad, 1);
-        int64_t tot;
-        const int64_t ex = block_excl_scan<kScanBlock>((int64_t)(len < 0 ? 0 : len), tot);
-        if (i < S) w.off[f * S + i] = carry + ex;
-        carry += tot;
-        unsigned long long ta = 0, tb = 0, all;
-        if (i < S) {
-            const int64_t end = (i + 1) * kStrip < stream_bytes ? (i + 1) * kStrip : stream_bytes;
-            ta = w.sum_a[f * S + i];
-            tb = w.sum_b[f * S + i] + (unsigned long long)((stream_bytes - end) % kAdler) * ta;
-        }
-        block_excl_scan<kScanBlock>(ta, all);
-        sa += all;
-        block_excl_scan<kScanBlock>(tb, all);
-        sb += all;
-    }
+    const int64_t bits = nerfhip::block_offsets_scan<kScanBlock>(
+        S, w.off + f * S, [&](int64_t i) { return nerfhip::strip_bits_or_flag(w.bitlen[f * S + i], &bad); },
+        [&](int64_t i) {                                    // the pass's Adler terms, summed over the workgroup
+            unsigned long long ta = 0, tb = 0, all;
+            if (i < S) {
+                const int64_t end = (i + 1) * kStrip < stream_bytes ? (i + 1) * kStrip : stream_bytes;
+                ta = w.sum_a[f * S + i];
+                tb = w.sum_b[f * S + i] + (unsigned long long)((stream_bytes - end) % kAdler) * ta;
+            }
+            block_excl_scan<kScanBlock>(ta, all);
+            sa += all;
+            block_excl_scan<kScanBlock>(tb, all);
+            sb += all;
+        });
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int64_t n = (carry + 7) / 8;
-        w.total[f] = carry;
+        const int64_t n = (bits + 7) / 8;
+        w.total[f] = bits;
         lengths[f] = (bad || n > 0x7fffffff) ? -1 : (int32_t)n;
         const uint32_t lo = (uint32_t)((1 + sa) % kAdler), hi = (uint32_t)(((unsigned long long)(stream_bytes % kAdler) + sb) % kAdler);
         adler[f] = hi << 16 | lo;
     }
 }
 
-// Gather: one thread per byte of the stream's deflate data.  It finds the strip that holds its first bit by binary search over
-// the offsets and collects its 8 bits from that strip and the next ones; the bits behind the last strip are zero.  No byte has
-// two writers.
+// Gather: one thread per byte of the stream's deflate data: gather_byte (strip_bits.h) of its first bit; the bits behind the
+// last strip are zero.  No byte has two writers.
 __global__ void __launch_bounds__(kBlock) png_gather(int64_t S, int64_t stride, PngWs w, const int32_t* __restrict__ lengths,
                                                      unsigned char* __restrict__ data) {
     const int64_t f = blockIdx.y;
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= (int64_t)lengths[f] || p >= stride) return;      // (-1: the stream failed, nothing is written)
-    const int64_t* off = w.off + f * S;
-    const int32_t* len = w.bitlen + f * S;
-    int64_t bit = 8 * p;
-    int64_t lo = 0, hi = S - 1;                 // the last strip whose offset is <= bit
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= bit) lo = mid; else hi = mid - 1;
-    }
-    int64_t s = lo;
-    int got = 0;
-    unsigned v = 0;
-    while (got < 8 && s < S) {
-        const int64_t q = bit - off[s];
-        const int avail = (int)(len[s] - q);
-        if (avail <= 0) { ++s; continue; }
-        const int take = avail < 8 - got ? avail : 8 - got;
-        const uint32_t* words = w.bits + (f * S + s) * kStripWords;
-        const int word = (int)(q >> 5), sh = (int)(q & 31);
-        unsigned long long x = words[word];
-        if (sh + take > 32) x |= (unsigned long long)words[word + 1] << 32;
-        v |= (unsigned)((x >> sh) & ((1u << take) - 1u)) << got;
-        got += take;
-        bit += take;
-    }
-    data[f * stride + p] = (unsigned char)v;
+    data[f * stride + p] = (unsigned char)nerfhip::gather_byte(w.off + f * S, w.bitlen + f * S, w.bits, f * S, S, kStripWords, 8 * p);
 }
 
 bool stream_ok(int n, int64_t stream_bytes) { return n >= 0 && n <= 65535 && stream_bytes >= 1 && stream_bytes < ((int64_t)1 << 31); }

@@ -1,6 +1,7 @@
 // The Unity volume file (extract_mesh.ipynb, cell "Generate .vol file for volume rendering in Unity"): quantise rgb-sigma to
 // RGBA bytes and keep, in index order, the lattice points whose alpha is positive.  One thread per point; the only cross-block
-// communication is the block-total scan (one workgroup) between two launches.  Passes and byte counts: DESIGN.md, volume export.
+// communication is the block-total scan (one workgroup, block_scan.h's offsets scan) between two launches.  Passes and byte
+// counts: DESIGN.md, volume export.
 #include <math.h>
 
 #include "block_scan.h"
@@ -9,6 +10,7 @@
 namespace {
 
 using nerfhip::block_excl_scan;
+using nerfhip::carve;
 
 constexpr int kBlock = 256;        // threads of the two per-point kernels (4 waves)
 constexpr int kScanBlock = 1024;   // the single workgroup that scans the block totals
@@ -19,16 +21,16 @@ struct VolWs {
     int32_t* blk;      // (nb) kept points per block
 };
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int64_t vol_blocks(int64_t n) { return (n + kBlock - 1) / kBlock; }
 
-inline VolWs vol_ws(void* base, int64_t n) {
+inline VolWs vol_ws(void* base, int64_t n, size_t* bytes) {
     const int64_t nb = vol_blocks(n);
     char* p = (char*)base;
     VolWs w;
-    w.base = (int64_t*)p; p += 256;
-    w.off = (int64_t*)p; p += align256(8 * nb);
-    w.blk = (int32_t*)p; p += align256(4 * nb);
+    w.base = carve<int64_t>(p, 1);
+    w.off = carve<int64_t>(p, nb);
+    w.blk = carve<int32_t>(p, nb);
+    if (bytes) *bytes = (size_t)(p - (char*)base);
     return w;
 }
 
@@ -62,19 +64,11 @@ __global__ void __launch_bounds__(kBlock) vol_count(const float4* __restrict__ r
 
 // One workgroup: exclusive offsets of the block totals; the device cursor is read (-> *w.base) and advanced by the call's count.
 __global__ void __launch_bounds__(kScanBlock) vol_scan(int64_t nb, VolWs w, int64_t* __restrict__ cursor) {
-    int64_t carry = 0;
-    for (int64_t base = 0; base < nb; base += kScanBlock) {
-        const int64_t i = base + threadIdx.x;
-        const int64_t v = i < nb ? (int64_t)w.blk[i] : 0;
-        int64_t tot;
-        const int64_t ex = block_excl_scan<kScanBlock>(v, tot);
-        if (i < nb) w.off[i] = carry + ex;
-        carry += tot;
-    }
+    const int64_t kept = nerfhip::block_offsets_scan<kScanBlock>(nb, w.off, [&](int64_t i) { return w.blk[i]; });
     if (threadIdx.x == 0) {
         const int64_t c = *cursor;
         *w.base = c;
-        *cursor = c + carry;
+        *cursor = c + kept;
     }
 }
 
@@ -100,8 +94,9 @@ inline bool vol_n_ok(int64_t n) { return n >= 0 && n <= ((int64_t)1 << 32); }
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------
 extern "C" size_t nerfhip_vol_workspace_bytes(int64_t n) {
     if (!vol_n_ok(n)) return 0;
-    const int64_t nb = vol_blocks(n);
-    return 256 + align256(8 * nb) + align256(4 * nb);
+    size_t bytes = 0;
+    vol_ws(nullptr, n, &bytes);
+    return bytes;
 }
 
 extern "C" int nerfhip_vol_pack(const float* rgbsigma, int64_t n, int64_t first_index, float neg_cell, void* workspace,
@@ -111,7 +106,7 @@ extern "C" int nerfhip_vol_pack(const float* rgbsigma, int64_t n, int64_t first_
     NERFHIP_CHECK_ARG(rgbsigma && workspace && records && cursor);
     if ((((uintptr_t)rgbsigma) & 15) || (((uintptr_t)records) & 7) || (((uintptr_t)workspace) & 7) || (((uintptr_t)cursor) & 7))
         return NERFHIP_E_ALIGN;
-    const VolWs w = vol_ws(workspace, n);
+    const VolWs w = vol_ws(workspace, n, nullptr);
     const unsigned nb = (unsigned)vol_blocks(n);        // <= 2^24
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(vol_count, dim3(nb), dim3(kBlock), 0, s, (const float4*)rgbsigma, n, neg_cell, w);

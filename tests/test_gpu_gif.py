@@ -111,6 +111,38 @@ def test_gpu_equals_the_restatement(dev, name):
         assert all(np.array_equal(got["palettes"][k][got["indices"][k]], want[k][1][want[k][0]].reshape(H, W, 3)) for k in range(F))
 
 
+def patched_indices(H, W, seed):
+    """(H, W) uint8 indices: constant tiles of 61 x 47 (long LZW strings) with 40 patches of noise (a new string per pixel)"""
+    rng = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    idx = ((yy // 61) * 7 + (xx // 47) * 13).astype(np.uint8)
+    for _ in range(40):
+        y, x, h, w = rng.randint(0, H - 100), rng.randint(0, W - 100), rng.randint(5, 100), rng.randint(5, 100)
+        idx[y:y + h, x:x + w] = rng.randint(0, 256, (h, w))
+    return idx
+
+
+def test_more_strips_than_one_pass_of_the_offsets_scan(dev):
+    """1025 strips, the last of 194 pixels: gif_scan's 1024-wide workgroup carries its sum into a second pass, and gif_gather
+    searches offsets written by both.  The LZW data goes into the container by the pieces GifWriter uses, with a grey palette,
+    and Pillow decodes it: the red channel is the index."""
+    import io
+    Image = pytest.importorskip("PIL.Image")
+    from nerf_pl_amd import imageio_min, ops
+    H, W = 1983, 1982
+    assert -(-H * W // K) == 1025 and H * W - 1024 * K == 194
+    idx = patched_indices(H, W, seed=12)
+    data, lengths = ops.gif_lzw(torch.from_numpy(idx.reshape(1, -1)).to(dev), H, W)
+    length = int(lengths[0])
+    assert length >= 0
+    grey = np.arange(256, dtype=np.uint8).repeat(3).tobytes()
+    whole = b"".join([imageio_min._gif_header(W, H), imageio_min._gif_frame_header(W, H, 30), grey, b"\x08",
+                      data[0, :length].cpu().numpy().tobytes(), b"\x00\x3b"])
+    im = Image.open(io.BytesIO(whole))
+    assert im.n_frames == 1 and im.size == (W, H)
+    assert np.array_equal(np.asarray(im.convert("RGB"))[:, :, 0], idx)
+
+
 def test_no_frames_and_write_gif(dev, tmp_path):
     from nerf_pl_amd import imageio_min, ops
     idx, pal, boxes = ops.gif_quantize(torch.zeros((0, 5, 7, 3), device=dev, dtype=torch.uint8))

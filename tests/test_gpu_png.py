@@ -67,6 +67,29 @@ def test_crafted_streams_reach_the_coder_directly(dev):
         assert got == png_ref.deflate(stream), name
 
 
+def runs_and_literals(n, seed):
+    """n bytes over a 16-value alphabet: a seeded mix of short pieces (1..3 bytes: literals) and runs of up to 300 (matches)."""
+    rng = np.random.RandomState(seed)
+    count = n // 40                                                # mean piece length is about 76: more than n bytes in all
+    length = np.where(rng.rand(count) < 0.5, rng.randint(1, 4, count), rng.randint(1, 301, count))
+    out = np.repeat(rng.randint(0, 16, count).astype(np.uint8), length)
+    assert out.size >= n
+    return np.ascontiguousarray(out[:n])
+
+
+def test_more_strips_than_one_pass_of_the_offsets_scan(dev):
+    """1025 strips, the last of one byte: png_scan's 1024-wide workgroup carries its sums into a second pass, and png_gather
+    searches offsets written by both.  The restatement's per-strip Python is too slow here: the oracle is zlib on the host."""
+    import zlib
+    from nerf_pl_amd import ops
+    stream = runs_and_literals(1024 * ops.PNG_STRIP + 1, seed=11)
+    data, lengths, adler = ops.png_deflate(torch.from_numpy(stream[None]).to(dev))
+    length = int(lengths[0])
+    assert length >= 0
+    assert int(adler[0]) & 0xffffffff == zlib.adler32(stream.tobytes())
+    assert zlib.decompress(data[0, :length].cpu().numpy().tobytes(), -15) == stream.tobytes()
+
+
 def test_batches_give_the_same_bytes_per_image(dev, cases):
     from nerf_pl_amd import imageio_min
     frames = dict(np.load(os.path.join(ROOT, "tests", "golden", "gif_mini", "frames.npz")))
