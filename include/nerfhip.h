@@ -622,6 +622,73 @@ int nerfhip_jpeg_decode(const int16_t* coef_y, const int16_t* coef_cb, const int
                         uint8_t* planes, uint8_t* out, int n_images, int H, int W, int n_comp, int hs, int vs,
                         nerfhip_stream_t stream);
 
+/* ---- Huffman-decoding the scans on the device  (DESIGN.md "Scene loading": the entropy stage on the GPU) ----------------------
+ * A batch of n_images baseline scans of one frame size and sampling goes up as the files' bytes and comes out as the coefficient
+ * tensors jpeg_decode takes, bit-equal to jpeg_entropy_decode's.  The stream of every restart interval is cut into subsequences
+ * of subseq_bits bits, one thread each; threads carry their exit state (bit position, block inside the MCU, zigzag index) on
+ * into the following subsequences until the records agree (self-synchronisation).  The Huffman tables are built on the device
+ * from the same 272-byte definitions the host entry takes.
+ *
+ * All pointers of the batch are device pointers, `comp` excepted, which sits in the struct:
+ *   scans              the scans' bytes back to back (total_bytes of them; read byte by byte, no padding needed)
+ *   offsets            (n_images + 1) int64, 8-byte aligned: scan i is [offsets[i], offsets[i + 1])
+ *   huffman            (n_images, 8, 272) uint8 and huffman_masks (n_images) int32, as jpeg_entropy_decode's
+ *   restart_intervals  (n_images) int32, in MCUs, 0 = none: the files of a batch may differ in it
+ *   max_scan_bytes     at least the longest scan (1 .. 2^28); max_intervals: at least the most restart intervals of any image,
+ *                      ceil(mcus_x * mcus_y / restart_interval), 1 without restarts.  Both size the workspace and the grids; an
+ *                      image that exceeds either, or whose offsets are not increasing inside total_bytes, gets status BADARG.
+ *   comp               (n_comp, 4) int32 = h, v, DC table id, AC table id, as jpeg_entropy_decode's; at most 6 blocks per MCU
+ *   subseq_bits        a multiple of 32 in 32 .. 4096
+ *   workspace          jpeg_entropy_workspace_bytes(...) bytes, 256-byte aligned (NERFHIP_E_ALIGN); it carries the state from
+ *                      jpeg_entropy_sync over jpeg_entropy_rounds to jpeg_entropy_emit
+ *   status             (n_images) int32, written by sync and emit: 0, NERFHIP_E_DATA (a truncated scan, an invalid code, a size or
+ *                      index out of range, a wrong or missing RSTm marker, a table that is no prefix code or is missing: whatever
+ *                      jpeg_entropy_decode refuses) or NERFHIP_E_BADARG.  The other images of the batch are not affected.
+ *   progress           one int32: the number of the last round between workgroups that changed a record (0: none since the
+ *                      passes inside the workgroups).  The records are final once a round has run that changed nothing, i.e.
+ *                      when progress < the number of the last round enqueued; (workgroups + 1) rounds always suffice.
+ * Nothing allocates or synchronises; arguments are validated before anything is launched (NERFHIP_E_BADARG / NERFHIP_E_ALIGN).
+ *   jpeg_entropy_workgroups  workgroups (of 256 subsequences) per image for these sizes: the bound of the host's loop; 0 = refused
+ *   jpeg_entropy_sync        prepare (classify and compact the bytes, cut at the RSTm markers, build the tables), the passes
+ *                            inside every workgroup, then rounds 1 .. `rounds` (0 .. 64) between workgroups
+ *   jpeg_entropy_rounds      rounds first_round .. first_round + rounds - 1; a round returns at once when the one before
+ *                            changed nothing
+ *   jpeg_entropy_emit        block offsets, the second decode from the true entry states into coef_* (n_images, blocks_c, 64)
+ *                            int16, which the caller has zeroed (coef_cb / coef_cr NULL when n_comp == 1), DC differences ->
+ *                            DC values.  An image whose status is not 0 is left with undefined coefficients.
+ * The caller reads status and progress between sync / rounds and emit (one synchronisation per batch), and enqueues more rounds
+ * while progress says so.
+ *
+ * jpeg_entropy_decode_split: HOST function — host pointers only (also workspace, status, progress), no GPU, launches nothing.  The
+ * same arguments, the same four steps with the same per-symbol code over the same subsequences, the threads of a workgroup and
+ * the workgroups of a round in lockstep.  It exists so that the algorithm, its bounds and its error paths can be tested and run
+ * under a sanitizer on a machine without a GPU.  Returns 0 when it ran (the images' results are in status).                      */
+typedef struct nerfhip_jpeg_batch {
+    const uint8_t* scans;
+    const int64_t* offsets;
+    const uint8_t* huffman;
+    const int32_t* huffman_masks;
+    const int32_t* restart_intervals;
+    int64_t total_bytes;
+    int64_t max_scan_bytes;
+    int32_t max_intervals;
+    int32_t n_images;
+    int32_t n_comp;
+    int32_t comp[12];
+    int32_t mcus_x, mcus_y;
+    int32_t subseq_bits;
+    void* workspace;
+    int32_t* status;
+    int32_t* progress;
+} nerfhip_jpeg_batch;
+size_t nerfhip_jpeg_entropy_workspace_bytes(int n_images, int64_t max_scan_bytes, int max_intervals, int subseq_bits);
+int nerfhip_jpeg_entropy_workgroups(int64_t max_scan_bytes, int max_intervals, int subseq_bits);
+int nerfhip_jpeg_entropy_sync(const nerfhip_jpeg_batch* batch, int rounds, nerfhip_stream_t stream);
+int nerfhip_jpeg_entropy_rounds(const nerfhip_jpeg_batch* batch, int first_round, int rounds, nerfhip_stream_t stream);
+int nerfhip_jpeg_entropy_emit(const nerfhip_jpeg_batch* batch, int16_t* coef_y, int16_t* coef_cb, int16_t* coef_cr,
+                              nerfhip_stream_t stream);
+int nerfhip_jpeg_entropy_decode_split(const nerfhip_jpeg_batch* batch, int16_t* coef_y, int16_t* coef_cb, int16_t* coef_cr);
+
 /* ---- scoring and logging rendered images  (metrics.py:15-20, utils/visualization.py:6-17; DESIGN.md "Image metrics") ---------
  * ssim: the reference's `metrics.ssim` = 1 - 2 * kornia.losses.ssim(img1, img2, window_size, reduction) as kornia 0.2.0 defines
  * it.  Window: outer product of g[i] = exp(-(i - ws/2)^2 / (2 * 1.5^2)) normalised to sum 1; depth-wise filter with zero padding

@@ -136,6 +136,12 @@ SIGNATURES = {
     "nerfhip_jpeg_planes_bytes": [_int, _int, _int, _int, _int],
     "nerfhip_jpeg_decode": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _int, _int, _int, _int, _int,
                             _c_void_p],
+    "nerfhip_jpeg_entropy_workspace_bytes": [_int, _i64, _int, _int],
+    "nerfhip_jpeg_entropy_workgroups": [_i64, _int, _int],
+    "nerfhip_jpeg_entropy_sync": [_c_void_p, _int, _c_void_p],
+    "nerfhip_jpeg_entropy_rounds": [_c_void_p, _int, _int, _c_void_p],
+    "nerfhip_jpeg_entropy_emit": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_jpeg_entropy_decode_split": [_c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "nerfhip_ssim_workspace_bytes": [_int, _int, _int, _int],
     "nerfhip_ssim": [_c_void_p, _c_void_p, _int, _int, _int, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "nerfhip_depth_colormap_workspace_bytes": [_i64],
@@ -181,6 +187,15 @@ class RenderArgs(ctypes.Structure):
                 ("ticket", _c_void_p), ("regen_enc", _int)]
 
 
+class JpegBatch(ctypes.Structure):
+    """include/nerfhip.h: nerfhip_jpeg_batch"""
+    _fields_ = [("scans", _c_void_p), ("offsets", _c_void_p), ("huffman", _c_void_p), ("huffman_masks", _c_void_p),
+                ("restart_intervals", _c_void_p), ("total_bytes", _i64), ("max_scan_bytes", _i64), ("max_intervals", ctypes.c_int32),
+                ("n_images", ctypes.c_int32), ("n_comp", ctypes.c_int32), ("comp", ctypes.c_int32 * 12), ("mcus_x", ctypes.c_int32),
+                ("mcus_y", ctypes.c_int32), ("subseq_bits", ctypes.c_int32), ("workspace", _c_void_p), ("status", _c_void_p),
+                ("progress", _c_void_p)]
+
+
 class EncSource(ctypes.Structure):
     """include/nerfhip.h: nerfhip_enc_source"""
     _fields_ = [("rays", _c_void_p * 2), ("z", _c_void_p * 2), ("S", _int * 2)]
@@ -194,7 +209,8 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_mlp_dw_workspace_bytes_multi": ctypes.c_size_t,
              "nerfhip_linear_bwd_weight_workspace_bytes": ctypes.c_size_t,
              "nerfhip_marching_cubes_workspace_bytes": ctypes.c_size_t, "nerfhip_mesh_cluster_workspace_bytes": ctypes.c_size_t,
-             "nerfhip_jpeg_planes_bytes": ctypes.c_size_t, "nerfhip_ssim_workspace_bytes": ctypes.c_size_t,
+             "nerfhip_jpeg_planes_bytes": ctypes.c_size_t, "nerfhip_jpeg_entropy_workspace_bytes": ctypes.c_size_t,
+             "nerfhip_ssim_workspace_bytes": ctypes.c_size_t,
              "nerfhip_depth_colormap_workspace_bytes": ctypes.c_size_t, "nerfhip_gif_workspace_bytes": ctypes.c_size_t,
              "nerfhip_gif_data_stride": ctypes.c_size_t, "nerfhip_vol_workspace_bytes": ctypes.c_size_t,
              "nerfhip_png_workspace_bytes": ctypes.c_size_t, "nerfhip_png_data_stride": ctypes.c_size_t}

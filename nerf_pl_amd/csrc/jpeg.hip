@@ -8,6 +8,7 @@
 //   jpeg_to_rgbx   reads 18.3 MB of planes (chroma neighbours come from cache), writes 48.8 MB
 // Both are memory-bound.  Timings: DESIGN.md, scene loading.
 #include "common.h"
+#include "jpeg_huff.h"
 
 namespace {
 
@@ -16,47 +17,10 @@ constexpr int kDctPerGroup = kBlock / 8; // 8 lanes own one 8 x 8 block, so a wa
 constexpr int kPad = 9;                  // LDS row stride in dwords: a column read of 8 lanes lands on 8 different banks
 
 // ---- entropy decoding (host) ---------------------------------------------------------------------------------------------------
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-constexpr int kLook = 9;                 // bits resolved by one table lookup
-
-struct HuffTable {
-    bool present = false;
-    uint16_t look[1 << kLook];           // (length << 8) | symbol for codes of up to kLook bits, 0 = longer or invalid
-    int32_t maxcode[18];                 // largest code of each length (-1: none), canonical decoding for the longer ones
-    int32_t valptr[17];
-    int32_t mincode[17];
-    uint8_t symbols[256];
-};
-
-// counts[16] + symbols[256] -> decoding tables.  False when the counts describe no prefix code (over-subscribed or > 256 symbols).
-bool build_table(const uint8_t* def, HuffTable& t) {
-    int total = 0;
-    for (int l = 0; l < 16; ++l) total += def[l];
-    if (total < 1 || total > 256) return false;
-    for (int i = 0; i < 256; ++i) t.symbols[i] = def[16 + i];
-    for (int i = 0; i < (1 << kLook); ++i) t.look[i] = 0;
-    int code = 0, k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        const int n = def[l - 1];
-        t.valptr[l] = k;
-        t.mincode[l] = code;
-        if (code + n > (1 << l)) return false;
-        for (int i = 0; i < n; ++i, ++k, ++code) {
-            if (l <= kLook) {
-                const int first = code << (kLook - l);
-                for (int j = 0; j < (1 << (kLook - l)); ++j) t.look[first + j] = (uint16_t)((l << 8) | t.symbols[k]);
-            }
-        }
-        t.maxcode[l] = n ? code - 1 : -1;
-        code <<= 1;
-    }
-    t.maxcode[17] = 0x7fffffff;
-    t.present = true;
-    return true;
-}
+// (the tables and the zigzag order: jpeg_huff.h, shared with the split decoder of jpeg_entropy.hip)
+using nerfhip::jpeg::HuffTable;
+using nerfhip::jpeg::build_table;
+using nerfhip::jpeg::kLook;
 
 // MSB-first bit reader over the entropy-coded bytes of one restart interval.  Reads past the end deliver zeros and are
 // counted: the caller checks `overrun()` after each block, so no input byte outside [p, end) is ever touched.
@@ -144,7 +108,7 @@ inline int decode_block(BitReader& br, const HuffTable& dc, const HuffTable& ac,
         }
         k += r;
         if (k > 63 || s > 10) return NERFHIP_E_DATA;
-        out[kZigzag[k]] = (int16_t)receive_extend(br, s);
+        out[nerfhip::jpeg::zigzag(k)] = (int16_t)receive_extend(br, s);
         ++k;
     }
     return br.overrun() ? NERFHIP_E_DATA : 0;

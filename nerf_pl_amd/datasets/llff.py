@@ -4,7 +4,8 @@ the device.
 The host reads each image file, parses its markers and Huffman-decodes the scan (imageio_min.jpeg_parse,
 ops.jpeg_entropy_decode: C++, no GPU); the coefficient blocks go to HBM and the inverse DCT, chroma upsampling, colour
 conversion, Pillow's Lanczos resize and ToTensor run as HIP kernels (csrc/jpeg.hip, csrc/image.hip) whose bytes and floats
-equal what the reference's PIL + torchvision pipeline produces.  A file with the PNG signature in `images/` takes the PNG path
+equal what the reference's PIL + torchvision pipeline produces.  With jpeg_entropy="gpu" the scans are uploaded as the files' bytes and
+Huffman-decoded on the device as well (ops.jpeg_entropy_decode_batch, csrc/jpeg_entropy.hip), to the same coefficients.  A file with the PNG signature in `images/` takes the PNG path
 of the Blender loader.  The COLMAP pose handling stays on the host in float64 numpy, as in the reference.  Attribute names and
 semantics are the reference's; tensors live on the device."""
 import glob
@@ -76,9 +77,14 @@ def create_spheric_poses(radius, n_poses=120):
 
 
 class LLFFDataset(torch.utils.data.Dataset):
-    def __init__(self, root_dir, split='train', img_wh=(504, 378), spheric_poses=False, val_num=1, device=None):
+    def __init__(self, root_dir, split='train', img_wh=(504, 378), spheric_poses=False, val_num=1, device=None, jpeg_entropy="host"):
         """spheric_poses: the images were taken facing inwards around an object (default: forward-facing, NDC rays)
-        val_num: number of val images (the same image, once per GPU)"""
+        val_num: number of val images (the same image, once per GPU)
+        jpeg_entropy: "host" Huffman-decodes every JPEG scan on the CPU (ops.jpeg_entropy_decode) and uploads the coefficients;
+        "gpu" uploads the scans' bytes and decodes each batch on the device (ops.jpeg_entropy_decode_batch).  Same colours."""
+        if jpeg_entropy not in ("host", "gpu"):
+            raise ValueError('jpeg_entropy must be "host" or "gpu", got %r' % (jpeg_entropy,))
+        self.jpeg_entropy = jpeg_entropy
         self.root_dir = root_dir
         self.split = split
         self.img_wh = img_wh
@@ -144,8 +150,8 @@ class LLFFDataset(torch.utils.data.Dataset):
 
     # ---- image files -> colours --------------------------------------------------------------------------------------------
     def _read(self, path):
-        """One file -> ('png', (W, H, ch), stream) or ('jpeg', (W, H, n_comp, hs, vs), (coefficient blocks, quantisation tables)),
-        by the file's signature."""
+        """One file -> ('png', (W, H, ch), stream) or ('jpeg', (W, H, n_comp, hs, vs), (coefficient blocks — or, with
+        jpeg_entropy="gpu", the parsed file —, quantisation tables)), by the file's signature."""
         with open(path, "rb") as f:
             data = f.read()
         if data[:8] == b"\x89PNG\r\n\x1a\n":
@@ -162,7 +168,10 @@ class LLFFDataset(torch.utils.data.Dataset):
         parsed["name"] = path
         comps = parsed["components"]
         quant = np.stack([parsed["quant"][c[3]] for c in comps]).astype(np.int16)
-        return 'jpeg', (parsed["width"], parsed["height"], len(comps), comps[0][1], comps[0][2]), (ops.jpeg_entropy_decode(parsed), quant)
+        shape = (parsed["width"], parsed["height"], len(comps), comps[0][1], comps[0][2])
+        if self.jpeg_entropy == "gpu":       # the scan stays as the file's bytes: _decode decodes the batch on the device
+            return 'jpeg', shape, (parsed, quant)
+        return 'jpeg', shape, (ops.jpeg_entropy_decode(parsed), quant)
 
     def _decode(self, kind, shape, items):
         """Files of one kind and shape -> (n, H, W, 4) uint8 on the device, alpha 255."""
@@ -173,7 +182,10 @@ class LLFFDataset(torch.utils.data.Dataset):
             rgbx[..., :3] = px[..., :3]                  # convert('RGB') drops the alpha channel
             return rgbx
         W, H, n_comp, hs, vs = shape
-        coefs = [torch.from_numpy(np.stack([it[0][c].reshape(-1, 64) for it in items])).to(self.device) for c in range(n_comp)]
+        if self.jpeg_entropy == "gpu":
+            coefs = ops.jpeg_entropy_decode_batch([it[0] for it in items], self.device)
+        else:
+            coefs = [torch.from_numpy(np.stack([it[0][c].reshape(-1, 64) for it in items])).to(self.device) for c in range(n_comp)]
         quant = torch.from_numpy(np.stack([it[1] for it in items])).to(self.device)
         return ops.decode_jpeg_batch(coefs, quant, H, W, hs, vs)
 

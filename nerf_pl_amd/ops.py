@@ -1360,3 +1360,152 @@ def decode_jpeg_batch(coefs, quant, H, W, hs=1, vs=1):
     check(lib.nerfhip_jpeg_decode(ptr(flat[0]), ptr(flat[1]) if n_comp == 3 else None, ptr(flat[2]) if n_comp == 3 else None,
                                   ptr(quant), ptr(planes), ptr(out), n, H, W, n_comp, hs, vs, stream_ptr()), "nerfhip_jpeg_decode")
     return out
+
+
+# ----------------------------------------------------------------------- the entropy stage on the device (csrc/jpeg_entropy.hip)
+def _jpeg_batch_arrays(what, parsed_list, subseq_bits):
+    """What nerfhip_jpeg_batch holds for these files (dicts of imageio_min.jpeg_parse, all of one size, sampling and component
+    count) as numpy arrays: (scans, offsets, huffman, masks, restart, comp, (mx, my), max_scan_bytes, max_intervals)."""
+    import numpy as np
+    parsed_list = list(parsed_list)
+    if not parsed_list:
+        raise NerfHipError("%s: no files" % what)
+    subseq_bits = int(subseq_bits)
+    if subseq_bits < 32 or subseq_bits > 4096 or subseq_bits % 32:
+        raise NerfHipError("%s: subseq_bits must be a multiple of 32 between 32 and 4096, got %d" % (what, subseq_bits))
+
+    def shape_of(p):
+        return (int(p["width"]), int(p["height"]), int(p["mcus_x"]), int(p["mcus_y"]), tuple((c[1], c[2]) for c in p["components"]))
+
+    def name_of(i):
+        return parsed_list[i].get("name", "file %d of the batch" % i)
+    first = parsed_list[0]
+    for i, p in enumerate(parsed_list[1:], 1):
+        if shape_of(p) != shape_of(first):
+            raise NerfHipError("%s: %s (%d x %d, sampling %s) and %s (%d x %d, sampling %s) differ in size, sampling or component "
+                               "count: one batch holds files of one shape" % ((what, name_of(0)) + shape_of(first)[:2]
+                                                                              + (shape_of(first)[4], name_of(i)) + shape_of(p)[:2]
+                                                                              + (shape_of(p)[4],)))
+    n = len(parsed_list)
+    mx, my = int(first["mcus_x"]), int(first["mcus_y"])
+    huffman = np.zeros((n, 8, 272), np.uint8)
+    masks = np.zeros(n, np.int32)
+    restart = np.zeros(n, np.int32)
+    offsets = np.zeros(n + 1, np.int64)
+    for i, p in enumerate(parsed_list):
+        for (tc, th), (counts, symbols) in p["huffman"].items():
+            huffman[i, 4 * tc + th, :16] = counts
+            huffman[i, 4 * tc + th, 16:16 + len(symbols)] = symbols
+            masks[i] |= 1 << (4 * tc + th)
+        restart[i] = int(p["restart_interval"])
+        offsets[i + 1] = offsets[i] + len(p["scan"])
+        if len(p["scan"]) < 1:
+            raise NerfHipError("%s: %s has an empty scan" % (what, name_of(i)))
+    scans = np.frombuffer(b"".join(bytes(p["scan"]) for p in parsed_list), np.uint8)
+    # the component rows may name different tables from file to file only if the tables' ids do: they are the scan header's
+    comp = np.ascontiguousarray([[c[1], c[2], c[4], c[5]] for c in first["components"]], dtype=np.int32)
+    for i, p in enumerate(parsed_list[1:], 1):
+        if [tuple(c[4:6]) for c in p["components"]] != [tuple(c[4:6]) for c in first["components"]]:
+            raise NerfHipError("%s: %s and %s assign their Huffman tables to the components differently" % (what, name_of(0), name_of(i)))
+    n_mcu = mx * my
+    max_intervals = max(-(-n_mcu // int(r)) if r > 0 else 1 for r in restart)
+    return scans, offsets, huffman, masks, restart, comp, (mx, my), int(np.diff(offsets).max()), int(max_intervals)
+
+
+def _jpeg_batch_struct(ptr_of, arrays, subseq_bits, workspace, status, progress):
+    scans, offsets, huffman, masks, restart, comp, (mx, my), max_scan, max_int = arrays
+    b = _lib.JpegBatch()
+    b.scans, b.offsets, b.huffman, b.huffman_masks, b.restart_intervals = (ptr_of(scans), ptr_of(offsets), ptr_of(huffman), ptr_of(masks),
+                                                                           ptr_of(restart))
+    b.total_bytes, b.max_scan_bytes, b.max_intervals, b.n_images, b.n_comp = int(scans.shape[0]), max_scan, max_int, len(masks), len(comp)
+    for i, v in enumerate(comp.reshape(-1).tolist()):
+        b.comp[i] = v
+    b.mcus_x, b.mcus_y, b.subseq_bits = mx, my, int(subseq_bits)
+    b.workspace, b.status, b.progress = ptr_of(workspace), ptr_of(status), ptr_of(progress)
+    return b
+
+
+def _jpeg_status_error(what, parsed_list, status):
+    bad = [i for i, s in enumerate(status) if s != 0]
+    if bad:
+        lib = _lib.load()
+        raise NerfHipError("; ".join("%s: %s failed: %s (code %d)" % (parsed_list[i].get("name", "file %d of the batch" % i), what,
+                                                                      lib.nerfhip_error_string(int(status[i])).decode(), int(status[i]))
+                                     for i in bad))
+
+
+def jpeg_entropy_decode_split(parsed_list, subseq_bits=1024, return_status=False):
+    """nerfhip_jpeg_entropy_decode_split (host, no GPU): the device entropy decoder's four steps run on the CPU over the same
+    subsequences -> per component an (n, blocks_y, blocks_x, 64) int16 numpy array.  For tests of the algorithm and its error
+    paths on a machine without a GPU; jpeg_entropy_decode is the host decoder to use.  return_status: (coefs, status (n,), rounds
+    between workgroups) instead of raising for a damaged file."""
+    import numpy as np
+    what = "jpeg_entropy_decode_split"
+    parsed_list = list(parsed_list)
+    arrays = _jpeg_batch_arrays(what, parsed_list, subseq_bits)
+    comp, (mx, my) = arrays[5], arrays[6]
+    n = len(parsed_list)
+    lib = _lib.load()
+    nbytes = lib.nerfhip_jpeg_entropy_workspace_bytes(n, arrays[7], arrays[8], int(subseq_bits))
+    if nbytes == 0:
+        raise NerfHipError("%s: sizes refused (scan of %d bytes, %d restart intervals)" % (what, arrays[7], arrays[8]))
+    raw = np.zeros(nbytes + 256, np.uint8)
+    workspace = raw[(-raw.ctypes.data) % 256:][:nbytes]
+    status, progress = np.zeros(n, np.int32), np.zeros(1, np.int32)
+    coefs = [np.zeros((n, my * c[1], mx * c[0], 64), np.int16) for c in comp]
+    b = _jpeg_batch_struct(lambda a: a.ctypes.data, arrays, subseq_bits, workspace, status, progress)
+    check(lib.nerfhip_jpeg_entropy_decode_split(ctypes.addressof(b), *[coefs[c].ctypes.data if c < len(coefs) else None for c in range(3)]),
+          "nerfhip_jpeg_entropy_decode_split")
+    if return_status:
+        return coefs, status, int(progress[0])
+    _jpeg_status_error("nerfhip_jpeg_entropy_decode_split", parsed_list, status)
+    return coefs
+
+
+_JPEG_ROUNDS_PER_CALL = 4     # rounds between workgroups enqueued before the host looks at the progress word
+
+
+def jpeg_entropy_decode_batch(parsed_list, device, subseq_bits=1024, return_rounds=False):
+    """nerfhip_jpeg_entropy_sync / _rounds / _emit: the scans of n JPEG files of one size and sampling (dicts of
+    imageio_min.jpeg_parse) are uploaded as the files' bytes and Huffman-decoded on the device -> per component an
+    (n, blocks_y, blocks_x, 64) int16 device tensor, bit-equal to jpeg_entropy_decode's and ready for decode_jpeg_batch.
+    One host synchronisation per batch (status and progress); more rounds between workgroups are enqueued only while the progress
+    word asks, at most (workgroups + 1).  subseq_bits: 1024 from the sweep of DESIGN §11 (256 to 1024 measure alike on a 12 MP
+    file, 2048 and 4096 slower).  Raises NerfHipError naming every file whose scan is damaged.  return_rounds: also the
+    number of rounds between workgroups that ran."""
+    import numpy as np
+    what = "jpeg_entropy_decode_batch"
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: %s got device %s (no CPU fallback)" % (what, device))
+    parsed_list = list(parsed_list)
+    arrays = _jpeg_batch_arrays(what, parsed_list, subseq_bits)
+    comp, (mx, my) = arrays[5], arrays[6]
+    n = len(parsed_list)
+    lib = _lib.load()
+    nbytes = lib.nerfhip_jpeg_entropy_workspace_bytes(n, arrays[7], arrays[8], int(subseq_bits))
+    wgs = lib.nerfhip_jpeg_entropy_workgroups(arrays[7], arrays[8], int(subseq_bits))
+    if nbytes == 0 or wgs == 0:
+        raise NerfHipError("%s: sizes refused (scan of %d bytes, %d restart intervals)" % (what, arrays[7], arrays[8]))
+    with torch.cuda.device(device):
+        dev = [torch.from_numpy(a.copy() if not a.flags.writeable else a).to(device) for a in arrays[:5]]
+        workspace = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        flags = torch.zeros(n + 1, device=device, dtype=torch.int32)             # status (n) and the progress word
+        coefs = [torch.zeros((n, my * int(c[1]), mx * int(c[0]), 64), device=device, dtype=torch.int16) for c in comp]
+        b = _jpeg_batch_struct(ptr, tuple(dev) + arrays[5:], subseq_bits, workspace, flags, flags[n:])
+        b.status, b.progress = flags.data_ptr(), flags.data_ptr() + 4 * n
+        enqueued = min(_JPEG_ROUNDS_PER_CALL, wgs + 1) if wgs > 1 else 0
+        check(lib.nerfhip_jpeg_entropy_sync(ctypes.addressof(b), enqueued, stream_ptr()), "nerfhip_jpeg_entropy_sync")
+        host = flags.cpu().numpy()
+        while wgs > 1 and host[n] >= enqueued and enqueued < wgs + 1 and not host[:n].all():
+            more = min(_JPEG_ROUNDS_PER_CALL, wgs + 1 - enqueued)
+            check(lib.nerfhip_jpeg_entropy_rounds(ctypes.addressof(b), enqueued + 1, more, stream_ptr()), "nerfhip_jpeg_entropy_rounds")
+            enqueued += more
+            host = flags.cpu().numpy()
+        check(lib.nerfhip_jpeg_entropy_emit(ctypes.addressof(b), *[ptr(coefs[c]) if c < len(coefs) else None for c in range(3)],
+                                            stream_ptr()), "nerfhip_jpeg_entropy_emit")
+        status = flags[:n].cpu().numpy()
+    _jpeg_status_error("nerfhip_jpeg_entropy_emit", parsed_list, status)
+    if return_rounds:
+        return coefs, int(host[n]) + 1 if wgs > 1 else 0
+    return coefs

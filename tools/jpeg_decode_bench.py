@@ -4,10 +4,17 @@ reference's own path on the same box, `Image.open().convert('RGB').resize(LANCZO
 gates nothing.
 
     python tools/jpeg_decode_bench.py [--out profiles/jpeg_decode_bench.json] [--reps 10] [--quality 90]
+    python tools/jpeg_decode_bench.py --entropy-out profiles/jpeg_entropy_bench.json      # also the entropy stage on the device
 
 Kernel times are hipEvent intervals around each operator call, the median of --reps runs after two warm-up runs; the achieved
 GB/s relate them to the kernels' algorithmic bytes (csrc/jpeg.hip).  The decode operator launches both kernels; to time them
-apart the 1-component form of the same call is timed as well (inverse DCT of the luma plane + the grey write)."""
+apart the 1-component form of the same call is timed as well (inverse DCT of the luma plane + the grey write).
+
+With --entropy-out the same file's scan is also Huffman-decoded on the device (csrc/jpeg_entropy.hip) for subseq_bits in 256, 512,
+1024, 2048 and 4096: hipEvent intervals around the launches of nerfhip_jpeg_entropy_sync (prepare, the passes inside the
+workgroups and the rounds between them that this file needs, found beforehand) and of nerfhip_jpeg_entropy_emit (with the zeroing
+of the coefficient tensors), buffers allocated and the scan uploaded outside the interval; the rounds each setting needed; the
+host-to-device bytes of both paths; and whether the coefficients equal the host decoder's."""
 import argparse
 import io
 import json
@@ -60,8 +67,64 @@ def device_ms(fn, reps):
     return statistics.median(out), r
 
 
+def device_entropy(parsed, coef, dev, reps, host_entropy_ms, h2d_bytes_host):
+    """the device entropy stage on one file, per subseq_bits"""
+    import ctypes
+    from nerf_pl_amd import _lib, ops
+    lib = _lib.load()
+    res = {"host_entropy_ms": host_entropy_ms, "h2d_bytes_host_path": h2d_bytes_host, "sweep": []}
+    for bits in (256, 512, 1024, 2048, 4096):
+        got, rounds = ops.jpeg_entropy_decode_batch([parsed], dev, bits, return_rounds=True)
+        equal = all(np.array_equal(g[0].cpu().numpy(), c) for g, c in zip(got, coef))
+        arrays = ops._jpeg_batch_arrays("bench", [parsed], bits)
+        up = [torch.from_numpy(a.copy()).to(dev) for a in arrays[:5]]
+        res["h2d_bytes_device_path"] = sum(t.numel() * t.element_size() for t in up)
+        nbytes = lib.nerfhip_jpeg_entropy_workspace_bytes(1, arrays[7], arrays[8], bits)
+        wgs = lib.nerfhip_jpeg_entropy_workgroups(arrays[7], arrays[8], bits)
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        flags = torch.zeros(2, device=dev, dtype=torch.int32)
+        b = ops._jpeg_batch_struct(ops.ptr, tuple(up) + arrays[5:], bits, ws, flags, flags[1:])
+        b.status, b.progress = flags.data_ptr(), flags.data_ptr() + 4
+
+        def sync():
+            ops.check(lib.nerfhip_jpeg_entropy_sync(ctypes.addressof(b), min(rounds, 64), ops.stream_ptr()), "sync")
+            done = min(rounds, 64)
+            while done < rounds:
+                more = min(64, rounds - done)
+                ops.check(lib.nerfhip_jpeg_entropy_rounds(ctypes.addressof(b), done + 1, more, ops.stream_ptr()), "rounds")
+                done += more
+
+        def emit():
+            for g in got:
+                g.zero_()
+            ops.check(lib.nerfhip_jpeg_entropy_emit(ctypes.addressof(b), *[ops.ptr(got[c]) if c < len(got) else None for c in range(3)],
+                                                    ops.stream_ptr()), "emit")
+        sync_ms, _ = device_ms(sync, reps)
+        emit_ms, _ = device_ms(emit, reps)
+        host = flags.cpu().numpy()
+        equal = equal and host[0] == 0 and host[1] < max(rounds, 1) and all(np.array_equal(g[0].cpu().numpy(), c) for g, c in zip(got, coef))
+        res["sweep"].append({"subseq_bits": bits, "workgroups": wgs, "rounds_between_workgroups": rounds, "sync_ms": sync_ms,
+                             "emit_ms": emit_ms, "device_entropy_ms": sync_ms + emit_ms, "workspace_bytes": nbytes,
+                             "equals_host_decoder": bool(equal)})
+    best = min(res["sweep"], key=lambda r: r["device_entropy_ms"])
+    res["fastest_subseq_bits"] = best["subseq_bits"]
+    res["device_over_host"] = best["device_entropy_ms"] / host_entropy_ms
+    return res
+
+
+def _rounded(x):
+    if isinstance(x, float):
+        return round(x, 4)
+    if isinstance(x, dict):
+        return {k: _rounded(v) for k, v in x.items()}
+    if isinstance(x, list):
+        return [_rounded(v) for v in x]
+    return x
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--entropy-out", default=None, help="also time the entropy stage on the device; its JSON goes here")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--quality", type=int, default=90)
@@ -108,6 +171,14 @@ def main():
     res["host_share"] = (res["parse_ms"] + res["entropy_ms"]) / res["ours_ms"]
     line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in res.items()})
     print(line)
+    if args.entropy_out:
+        ent = device_entropy(parsed, coef, dev, args.reps, res["entropy_ms"], res["h2d_bytes"])
+        ent.update(image=res["image"], device=res["device"], reps=args.reps)
+        ent_line = json.dumps(_rounded(ent))
+        print(ent_line)
+        os.makedirs(os.path.dirname(os.path.abspath(args.entropy_out)), exist_ok=True)
+        with open(args.entropy_out, "w") as f:
+            f.write(ent_line + "\n")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
