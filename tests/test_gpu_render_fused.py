@@ -34,14 +34,22 @@ CASES = [  # dtype, B, S, N, perturb, use_disp, noise_std, white_back, random u,
     ("fp32", 4, 32, 32, 0.0, True, 1.0, False, False, "blender"),
     ("fp32", 20, 64, 0, 1.0, False, 1.0, True, False, "ndc"),
     ("fp32", 8, 96, 32, 1.0, False, 0.0, True, True, "blender"),
+    ("bf16", 8, 64, 64, 1.0, False, 0.0, True, True, "far"),        # |x| <= 64 (oracle/ray_enc.py): the render kernels' copy of the encodings
 ]
+
+
+def _rays(seed, B, kind):
+    if kind == "far":
+        from oracle import ray_enc
+        return ray_enc.ray_cases("far", B, 1, seed)[0]
+    return O.make_rays(seed, B, kind)
 
 
 @pytest.mark.parametrize("dtype,B,S,N,perturb,use_disp,noise_std,white_back,rand_u,kind", CASES)
 def test_render_fwd_is_the_launches_it_replaces(dev, dtype, B, S, N, perturb, use_disp, noise_std, white_back, rand_u, kind):
     from nerf_pl_amd import ops
     ms, _ = _models(dev, dtype)
-    rays = O.make_rays(3, B, kind).to(dev)
+    rays = _rays(3, B, kind).to(dev)
     d = _draws(B, S, N, dev)
     pr = d["perturb_rand"] if perturb > 0 else None
     u = d["u"] if (rand_u and N > 0) else None
@@ -80,7 +88,7 @@ def test_render_test_fwd_is_the_five_launches_of_test_time(dev, dtype, B, S, N, 
     bit for bit: coarse depths, coarse sigma (B,S), coarse opacity, fine depths, fine rgb sigma, fine outputs."""
     from nerf_pl_amd import ops
     ms, _ = _models(dev, dtype)
-    rays = O.make_rays(4, B, kind).to(dev)
+    rays = _rays(4, B, kind).to(dev)
     d = _draws(B, S, N, dev, seed=1)
     pr = d["perturb_rand"] if perturb > 0 else None
     u = d["u"] if rand_u else None

@@ -837,18 +837,24 @@ def test_final_layer_fold_equals_the_direct_products_fp32(dev):
             assert err <= 1e-4 * r.abs().max().item() + 1e-9, (name, err, r.abs().max().item())
 
 
-@pytest.mark.parametrize("B,S", [(32, 64), (8, 192), (64, 32)])
-def test_dw_regenerated_encodings_are_the_saved_ones_bf16(dev, B, S):
+@pytest.mark.parametrize("B,S,kind", [pytest.param(32, 64, "blender", id="32-64"), pytest.param(8, 192, "blender", id="8-192"),
+                                      pytest.param(64, 32, "blender", id="64-32"), (32, 64, "far"), (32, 64, "knife")])
+def test_dw_regenerated_encodings_are_the_saved_ones_bf16(dev, B, S, kind):
     """nerfhip_mlp_bwd_multi_rays (bf16): the weight-gradient launch forms embedding_xyz(o + d z) and embedding_dir(d) (nerf.py:21-38,
     rendering.py:186,206-207) — the X operands of xyz_encoding_1, the skip layer and dir_encoding — from the rays and the depths
     instead of reading the six encoding slabs of every saved tile block.  Same arithmetic as the forward, so with those slabs
     NaN-poisoned the 24 gradients are BIT-identical to the ones computed from the saved slabs (one workgroup per job at this size:
-    the same split plan, hence the same summation order)."""
+    the same split plan, hence the same summation order).  `far` (|x| <= 64) and `knife` (points within two ulp of the places where
+    v_fract wraps: oracle/ray_enc.py) are the inputs on which two copies of the reduction compiled in different translation units —
+    contracted differently, say — would part."""
     from nerf_pl_amd import ops
     g = torch.Generator().manual_seed(3)
     (m,), _ = build_models([O.make_params(5, 3.0, 0.1)], dev, "bf16")
     rays = O.make_rays(9, B).to(dev)
     z = (2.0 + 4.0 * torch.rand(B, S, generator=g)).sort(-1)[0].to(dev)
+    if kind != "blender":
+        from oracle import ray_enc
+        rays, z = (t.to(dev) for t in ray_enc.ray_cases(kind, B, S))
     n = B * S
     acts = ops.alloc_acts(n, "bf16", dev)
     raw = ops.mlp_fwd_rays(rays, z, m.packed_weights("bf16"), False, "bf16", save=acts)
