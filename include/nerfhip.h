@@ -782,6 +782,33 @@ int nerfhip_png_deflate(const uint8_t* streams, int n, int64_t stream_bytes, uin
                         void* workspace, nerfhip_stream_t stream);
 int nerfhip_png_code_lengths(const uint32_t* counts, int n_symbols, int limit, uint8_t* lengths);
 
+/* ---- inflating PNG data  (datasets/blender.py:90 `img = Image.open(...)`, datasets/llff.py `Image.open(image_path)`)
+ * n_streams zlib streams (RFC 1950 around RFC 1951 deflate: stored, fixed and dynamic blocks, distances up to 32768, lengths up
+ * to 258) -> out (n_streams, out_stride) uint8, stream i's bytes at [i * out_stride, i * out_stride + out_bytes): the layout
+ * png_unfilter reads.  Nothing outside these ranges is written, whatever the streams hold.  One workgroup of one wave per stream;
+ * no workspace.
+ *   data       the streams back to back, total_bytes of them, read byte by byte (no alignment, no padding needed)
+ *   offsets    (n_streams + 1) int64, 8-byte aligned (NERFHIP_E_ALIGN): stream i is [offsets[i], offsets[i + 1]), at most 2^27 bytes
+ *   status     (n_streams) int32, 4-byte aligned, written by the launch: 0; NERFHIP_E_DATA for a stream that zlib's inflate
+ *              refuses (a header other than CM 8 / CINFO <= 7 / valid FCHECK / FDICT clear, block type 3, a stored block whose
+ *              lengths disagree, a code set that is over-subscribed or incomplete — the single one-bit code excepted —, no
+ *              end-of-block code, a repeat without a previous length or past HLIT + HDIST, HLIT > 286, HDIST > 30, an unassigned
+ *              code, symbols 286 / 287 / distance 30 / 31, a distance behind the first byte, missing bits, a wrong Adler-32) or
+ *              that produces more or fewer than out_bytes bytes; NERFHIP_E_BADARG for offsets that are not increasing inside
+ *              total_bytes.  The header's window size does not limit distances (zlib's default build does not either); bytes
+ *              behind the Adler-32 are ignored.  A damaged stream does not affect the others; its output bytes are undefined.
+ * n_streams == 0 is success and touches nothing; null pointers with bytes to read or write, negative sizes, out_stride < out_bytes
+ * and n_streams > 65535 are NERFHIP_E_BADARG before anything is launched.  Nothing allocates or synchronises.
+ *
+ * inflate_host: HOST function — host pointers only, no GPU, launches nothing.  The same arguments and verdicts from the same
+ * per-symbol code, table builder and copy steps (csrc/inflate_core.h), the 64 lanes of a stream's wave in lockstep.  It exists
+ * so that the algorithm, its bounds and its error paths can be tested and run under a sanitizer on a machine without a GPU.
+ * Returns 0 when it ran (the streams' results are in status).                                                                    */
+int nerfhip_inflate(const uint8_t* data, const int64_t* offsets, int64_t total_bytes, int n_streams, uint8_t* out, int64_t out_bytes,
+                    int64_t out_stride, int32_t* status, nerfhip_stream_t stream);
+int nerfhip_inflate_host(const uint8_t* data, const int64_t* offsets, int64_t total_bytes, int n_streams, uint8_t* out,
+                         int64_t out_bytes, int64_t out_stride, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,8 @@ SIGNATURES = {
     "nerfhip_png_filter": [_c_void_p, _int, _int, _int, _int, _c_void_p, _c_void_p],
     "nerfhip_png_deflate": [_c_void_p, _int, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
     "nerfhip_png_code_lengths": [_c_void_p, _int, _int, _c_void_p],
+    "nerfhip_inflate": [_c_void_p, _c_void_p, _i64, _int, _c_void_p, _i64, _i64, _c_void_p, _c_void_p],
+    "nerfhip_inflate_host": [_c_void_p, _c_void_p, _i64, _int, _c_void_p, _i64, _i64, _c_void_p],
 }
 
 

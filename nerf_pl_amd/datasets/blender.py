@@ -2,7 +2,8 @@
 
 The host reads each PNG and inflates it (zlib); the filtered scanlines go to HBM and the PNG reconstruction, Pillow's Lanczos
 resize, ToTensor and the blend onto white run as HIP kernels (csrc/image.hip) whose bytes and floats equal what the reference's
-PIL + torchvision pipeline produces.  Attribute names and semantics are the reference's; tensors live on the device."""
+PIL + torchvision pipeline produces.  With png_inflate="gpu" the files' IDAT data goes up as it stands and each batch is inflated
+on the device as well (ops.inflate_batch, csrc/inflate.hip), to the same scanlines.  Attribute names and semantics are the reference's; tensors live on the device."""
 import json
 import os
 
@@ -11,13 +12,18 @@ import torch
 
 from .. import ops, rays
 from .._lib import NerfHipError
-from ..imageio_min import png_inflate
+from ..imageio_min import png_idat, png_inflate
 
 _BATCH = 16            # images decoded per launch: bounds the uint8 staging (16 x 800 x 800 x 4 = 41 MB, three such buffers)
 
 
 class BlenderDataset(torch.utils.data.Dataset):
-    def __init__(self, root_dir, split='train', img_wh=(800, 800), device=None):
+    def __init__(self, root_dir, split='train', img_wh=(800, 800), device=None, png_inflate="host"):
+        """png_inflate: "host" inflates every file with zlib on the CPU and uploads the scanlines; "gpu" uploads the files' IDAT
+        bytes and inflates each batch on the device (ops.inflate_batch).  Same colours."""
+        if png_inflate not in ("host", "gpu"):
+            raise ValueError('png_inflate must be "host" or "gpu", got %r' % (png_inflate,))
+        self.png_inflate = png_inflate
         self.root_dir = root_dir
         self.split = split
         assert img_wh[0] == img_wh[1], 'image width must equal image height!'
@@ -64,17 +70,21 @@ class BlenderDataset(torch.utils.data.Dataset):
         """Files -> (rgb (len(paths) * h * w, 3) float32, valid_mask (len(paths) * h * w,) bool) on the device."""
         w, h = self.img_wh
         size, rows = None, []
+        gpu = self.png_inflate == "gpu"
         for p in paths:
-            W, H, ch, raw = png_inflate(p)
+            W, H, ch, raw = png_idat(p) if gpu else png_inflate(p)
             if ch != 4:
                 raise ValueError("%s: %d channels; Blender scenes are RGBA (the reference's view(4, -1) needs it too)" % (p, ch))
             if size is None:
                 size = (W, H)
             elif size != (W, H):
                 raise ValueError("%s is %d x %d, the files before it %d x %d" % (p, W, H, size[0], size[1]))
-            rows.append(np.frombuffer(raw, dtype=np.uint8))
+            rows.append(raw if gpu else np.frombuffer(raw, dtype=np.uint8))
         W, H = size
-        streams = torch.from_numpy(np.stack(rows)).to(self.device)
+        if gpu:
+            streams = ops.inflate_batch(rows, H * (1 + W * 4), self.device, names=list(paths))
+        else:
+            streams = torch.from_numpy(np.stack(rows)).to(self.device)
         rgba = ops.decode_png_batch(streams, H, W, 4)
         rgba = ops.resize_rgba_lanczos(rgba, w, h)
         return ops.rgba_to_rgb_white(rgba, out=out)

@@ -16,7 +16,7 @@ import torch
 
 from .. import ops, rays
 from .._lib import NerfHipError
-from ..imageio_min import jpeg_parse, png_inflate
+from ..imageio_min import jpeg_parse, png_idat, png_inflate
 
 _STAGING_BYTES = 256 << 20   # RGBX bytes decoded per batch: 5 images of 4032 x 3024 (48.8 MB each, 2.2 x that with the planes
                              # and coefficients beside it), any number of small ones up to _BATCH_MAX
@@ -77,14 +77,20 @@ def create_spheric_poses(radius, n_poses=120):
 
 
 class LLFFDataset(torch.utils.data.Dataset):
-    def __init__(self, root_dir, split='train', img_wh=(504, 378), spheric_poses=False, val_num=1, device=None, jpeg_entropy="host"):
+    def __init__(self, root_dir, split='train', img_wh=(504, 378), spheric_poses=False, val_num=1, device=None, jpeg_entropy="host",
+                 png_inflate="host"):
         """spheric_poses: the images were taken facing inwards around an object (default: forward-facing, NDC rays)
         val_num: number of val images (the same image, once per GPU)
         jpeg_entropy: "host" Huffman-decodes every JPEG scan on the CPU (ops.jpeg_entropy_decode) and uploads the coefficients;
-        "gpu" uploads the scans' bytes and decodes each batch on the device (ops.jpeg_entropy_decode_batch).  Same colours."""
+        "gpu" uploads the scans' bytes and decodes each batch on the device (ops.jpeg_entropy_decode_batch).  Same colours.
+        png_inflate: "host" inflates every PNG file with zlib on the CPU and uploads the scanlines; "gpu" uploads the files' IDAT
+        bytes and inflates each batch on the device (ops.inflate_batch).  Same colours."""
         if jpeg_entropy not in ("host", "gpu"):
             raise ValueError('jpeg_entropy must be "host" or "gpu", got %r' % (jpeg_entropy,))
+        if png_inflate not in ("host", "gpu"):
+            raise ValueError('png_inflate must be "host" or "gpu", got %r' % (png_inflate,))
         self.jpeg_entropy = jpeg_entropy
+        self.png_inflate = png_inflate
         self.root_dir = root_dir
         self.split = split
         self.img_wh = img_wh
@@ -155,9 +161,11 @@ class LLFFDataset(torch.utils.data.Dataset):
         with open(path, "rb") as f:
             data = f.read()
         if data[:8] == b"\x89PNG\r\n\x1a\n":
-            W, H, ch, raw = png_inflate(data)
+            W, H, ch, raw = png_idat(data) if self.png_inflate == "gpu" else png_inflate(data)
             if ch not in (3, 4):
                 raise ValueError("%s: a %d-channel PNG; RGB or RGBA expected" % (path, ch))
+            if self.png_inflate == "gpu":    # the IDAT data stays as the file's bytes: _decode inflates the batch on the device
+                return 'png', (W, H, ch), (path, raw)
             return 'png', (W, H, ch), np.frombuffer(raw, dtype=np.uint8)
         if data[:2] != b"\xff\xd8":
             raise ValueError("%s: neither a JPEG nor a PNG file" % path)
@@ -177,7 +185,11 @@ class LLFFDataset(torch.utils.data.Dataset):
         """Files of one kind and shape -> (n, H, W, 4) uint8 on the device, alpha 255."""
         if kind == 'png':
             W, H, ch = shape
-            px = ops.decode_png_batch(torch.from_numpy(np.stack(items)).to(self.device), H, W, ch)
+            if self.png_inflate == "gpu":
+                streams = ops.inflate_batch([it[1] for it in items], H * (1 + W * ch), self.device, names=[it[0] for it in items])
+            else:
+                streams = torch.from_numpy(np.stack(items)).to(self.device)
+            px = ops.decode_png_batch(streams, H, W, ch)
             rgbx = torch.full((len(items), H, W, 4), 255, device=self.device, dtype=torch.uint8)
             rgbx[..., :3] = px[..., :3]                  # convert('RGB') drops the alpha channel
             return rgbx

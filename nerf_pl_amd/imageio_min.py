@@ -66,10 +66,10 @@ def read_png(path):
     return out[:, :, 0].copy() if ch == 1 else out.copy()
 
 
-def png_inflate(data):
-    """PNG file contents (bytes, or a path) -> (w, h, channels, inflated IDAT stream).  The stream is h scanlines of
-    1 filter byte + w * channels bytes, still filtered: the GPU reverses the filters (ops.decode_png_batch).  Only what that
-    kernel takes is accepted: 8 bits per sample, no interlace, grey / RGB / RGBA."""
+def png_idat(data):
+    """PNG file contents (bytes, or a path) -> (w, h, channels, zlib stream): the IDAT chunks joined, not inflated (what
+    ops.inflate_batch takes).  Only what ops.decode_png_batch takes is accepted: 8 bits per sample, no interlace, grey / RGB /
+    RGBA."""
     if isinstance(data, str):
         with open(data, "rb") as f:
             data = f.read()
@@ -96,8 +96,15 @@ def png_inflate(data):
     if color not in (0, 2, 6):
         raise ValueError("PNG colour type %d (%s) is not supported (grey, RGB, RGBA only)"
                          % (color, {3: "palette", 4: "grey + alpha"}.get(color, "unknown")))
-    ch = {0: 1, 2: 3, 6: 4}[color]
-    raw = zlib.decompress(b"".join(idat))
+    return w, h, {0: 1, 2: 3, 6: 4}[color], b"".join(idat)
+
+
+def png_inflate(data):
+    """PNG file contents (bytes, or a path) -> (w, h, channels, inflated IDAT stream).  The stream is h scanlines of
+    1 filter byte + w * channels bytes, still filtered: the GPU reverses the filters (ops.decode_png_batch).  Only what that
+    kernel takes is accepted: 8 bits per sample, no interlace, grey / RGB / RGBA."""
+    w, h, ch, stream = png_idat(data)
+    raw = zlib.decompress(stream)
     if len(raw) != h * (1 + w * ch):
         raise ValueError("PNG data holds %d bytes, %d x %d x %d needs %d" % (len(raw), h, w, ch, h * (1 + w * ch)))
     return w, h, ch, raw

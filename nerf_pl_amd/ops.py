@@ -1509,3 +1509,74 @@ def jpeg_entropy_decode_batch(parsed_list, device, subseq_bits=1024, return_roun
     if return_rounds:
         return coefs, int(host[n]) + 1 if wgs > 1 else 0
     return coefs
+
+
+# --------------------------------------------------------------------------- inflating PNG data (csrc/inflate.hip)
+def _inflate_arrays(what, streams, out_bytes):
+    """The zlib streams (bytes-like) joined: (data uint8 (total,), offsets int64 (n + 1,))."""
+    import numpy as np
+    streams = [bytes(s) for s in streams]
+    out_bytes = int(out_bytes)
+    if out_bytes < 0:
+        raise NerfHipError("%s: out_bytes must not be negative, got %d" % (what, out_bytes))
+    if len(streams) > 65535:
+        raise NerfHipError("%s: at most 65535 streams per call, got %d" % (what, len(streams)))
+    offsets = np.zeros(len(streams) + 1, np.int64)
+    np.cumsum([len(s) for s in streams], out=offsets[1:])
+    return np.frombuffer(b"".join(streams), np.uint8), offsets, out_bytes
+
+
+def _inflate_status_error(what, names, status):
+    bad = [i for i, s in enumerate(status) if s != 0]
+    if bad:
+        lib = _lib.load()
+        raise NerfHipError("; ".join("%s: %s failed: %s (code %d)" % (names[i] if names is not None else "stream %d of the batch" % i, what,
+                                                                      lib.nerfhip_error_string(int(status[i])).decode(), int(status[i]))
+                                     for i in bad))
+
+
+def inflate_host(streams, out_bytes, return_status=False, names=None):
+    """nerfhip_inflate_host (host, no GPU): n zlib streams -> (n, out_bytes) uint8 numpy array, by the device decoder's own
+    per-symbol code with the lanes in lockstep.  For tests of the algorithm and its error paths on a machine without a GPU;
+    zlib.decompress is the host decoder to use.  return_status: (out, status (n,)) instead of raising for a damaged stream."""
+    import numpy as np
+    data, offsets, out_bytes = _inflate_arrays("inflate_host", streams, out_bytes)
+    n = len(offsets) - 1
+    out = np.zeros((n, out_bytes), np.uint8)
+    status = np.zeros(n, np.int32)
+    check(_lib.load().nerfhip_inflate_host(data.ctypes.data if data.size else None, offsets.ctypes.data, int(data.size), n,
+                                           out.ctypes.data if out.size else None, out_bytes, out_bytes, status.ctypes.data),
+          "nerfhip_inflate_host")
+    if return_status:
+        return out, status
+    _inflate_status_error("nerfhip_inflate_host", names, status)
+    return out
+
+
+def inflate_batch(streams, out_bytes, device, return_status=False, names=None):
+    """nerfhip_inflate: n zlib streams (bytes-like, e.g. imageio_min.png_idat's) are uploaded joined, in one copy with their
+    offsets, and inflated on the device -> (n, out_bytes) uint8 device tensor, ready for decode_png_batch.  One status read per
+    batch.  Raises NerfHipError naming every damaged stream (by `names[i]` where given); return_status: (out, status (n,) numpy)
+    instead."""
+    import numpy as np
+    what = "inflate_batch"
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: %s got device %s (no CPU fallback)" % (what, device))
+    data, offsets, out_bytes = _inflate_arrays(what, streams, out_bytes)
+    n = len(offsets) - 1
+    head = 8 * (n + 1)                                   # one upload: the offsets in front of the bytes
+    packed = np.empty(head + data.size, np.uint8)
+    packed[:head] = offsets.view(np.uint8)
+    packed[head:] = data
+    with torch.cuda.device(device):
+        up = torch.from_numpy(packed).to(device)
+        out = torch.empty((n, out_bytes), device=device, dtype=torch.uint8)
+        status = torch.zeros(max(n, 1), device=device, dtype=torch.int32)
+        check(_lib.load().nerfhip_inflate(up.data_ptr() + head, up.data_ptr(), int(data.size), n, out.data_ptr(), out_bytes, out_bytes,
+                                          status.data_ptr(), stream_ptr()), "nerfhip_inflate")
+        host = status[:n].cpu().numpy()
+    if return_status:
+        return out, host
+    _inflate_status_error("nerfhip_inflate", names, host)
+    return out

@@ -4,6 +4,7 @@
     python tools/kernel_digest.py > new.txt                      # every compile job of nerf_pl_amd.build
     python tools/kernel_digest.py mlp_bwd_chain mlp_dx           # only the jobs whose object name starts with one of these
     python tools/kernel_digest.py png gif                        # e.g. the PNG encoder's kernels beside the GIF's
+    python tools/kernel_digest.py inflate                        # the device inflate's one kernel
     python tools/kernel_digest.py jpeg                           # jpeg.hip's two kernels and jpeg_entropy.hip's seven
     python tools/kernel_digest.py --against old.txt > both.txt   # side by side with an earlier output, differences marked
 
