@@ -809,6 +809,53 @@ int nerfhip_inflate(const uint8_t* data, const int64_t* offsets, int64_t total_b
 int nerfhip_inflate_host(const uint8_t* data, const int64_t* offsets, int64_t total_bytes, int n_streams, uint8_t* out,
                          int64_t out_bytes, int64_t out_stride, int32_t* status);
 
+/* ---- skipping empty space at eval  (eval.py:58-86 `batched_inference` runs every sample of every ray) -----------
+ * Opt-in and beside the render path: an occupancy bitfield of the trained density, a per-ray cull against it that tightens
+ * [near, far] (columns 6 and 7 of the ray rows) or drops the ray, the stable compaction of the rays that are left and the
+ * scatter of their rendered values into full-size outputs.  No other entry point changes.  Every launch is one thread per cell,
+ * word or ray in 256-thread blocks.  Nothing is allocated, nothing synchronises.
+ *
+ * The bitfield (a public format).  sigma (N,N,N) fp32 as grid.sigma_grid returns it, indexed [iy, ix, iz]; 2 <= N <= 1025.  The
+ * grid has M = N - 1 cells per axis.  Cell (iy, ix, iz) is occupied iff one of its 8 corners sigma[iy + a, ix + b, iz + c],
+ * a, b, c in {0, 1}, is > threshold or NaN; then the set is dilated by `dilate` >= 0 cells in the Chebyshev metric, clipped at
+ * the grid's boundary (dilate >= M fills a grid that has one occupied cell).  words: ceil(M^3 / 32) int32, cell c = (iy M + ix) M
+ * + iz is bit c & 31 of word c >> 5, the unused bits of the last word are zero.  workspace: occupancy_workspace_bytes(N) bytes
+ * (2 M^3 rounded up to 256 each; 0 for a refused N).  The build is meant for small `dilate`: a dilation pass reads up to
+ * 2 dilate + 1 cells per cell (at most M), the pack 32 bytes per word; N = 256 with dilate <= 2 takes 0.07-0.26 ms, a dilate near
+ * M at N near 1025 would take on the order of M times longer per pass.
+ *
+ * cull_rays: rays (n,8) = [o d near far], 16-byte aligned, d of any length; words / M as above, 4-byte aligned
+ * (NERFHIP_E_ALIGN); ranges_host: 6 HOST floats x_lo x_hi y_lo y_hi z_lo z_hi, lo < hi; x runs along ix, y along iy, z along iz.
+ * Cell i of an axis spans [lo + i h, lo + (i + 1) h], h = (hi - lo) / M.  Per ray: hit (uint8), t0 = max(near, entry parameter
+ * of the first occupied cell the ray pierces), t1 = min(far, exit parameter of the last one); hit iff t0 < t1; a miss reports
+ * t0 = near, t1 = far.  A ray with a NaN or an infinity in any column is a hit with t0 = near, t1 = far.  Zero direction
+ * components of either sign are handled without a division.  0 <= n <= 2^30; n == 0 is success and touches nothing; null
+ * pointers with n > 0, M < 1, M > 1024 and ranges that are inverted, empty or not finite are NERFHIP_E_BADARG.
+ * cull_rays_host: HOST function — host pointers only, no GPU, launches nothing: the same per-ray routine
+ * (csrc/occupancy_core.h) in a loop, the same bits.
+ *
+ * cull_compact: hit, rays, t0, t1 as above -> slot (n) int32: the exclusive rank of ray i among the hits, -1 for a miss;
+ * index (n_hit) int32: the hits' ray numbers, ascending; rays_out (n_hit, 8): their rows with columns 6, 7 replaced by t0, t1
+ * (a null t0 or t1 keeps the row's own near or far; index and rays_out are sized for n rows); n_hit: one int32 on the DEVICE.
+ * workspace: cull_compact_workspace_bytes(n), 8-byte aligned.  n == 0 writes n_hit = 0 only.
+ *
+ * cull_scatter: for i < n and each output whose pointer is not null: out[i] = compact[slot[i]] when 0 <= slot[i] < n_compact,
+ * else the background: 1.0 (white_back) or 0.0 for rgb (n,3), 0.0 for depth and the two opacities (n) — what compositing gives
+ * for all-zero weights.  Any output may be null; an output without its compact source needs n_compact == 0.                     */
+size_t nerfhip_occupancy_workspace_bytes(int N);
+int nerfhip_occupancy_build(const float* sigma, int N, float threshold, int dilate, int32_t* words, void* workspace,
+                            nerfhip_stream_t stream);
+int nerfhip_cull_rays(const float* rays, int64_t n, const int32_t* words, int M, const float* ranges_host, uint8_t* hit, float* t0,
+                      float* t1, nerfhip_stream_t stream);
+int nerfhip_cull_rays_host(const float* rays, int64_t n, const int32_t* words, int M, const float* ranges_host, uint8_t* hit, float* t0,
+                           float* t1);
+size_t nerfhip_cull_compact_workspace_bytes(int64_t n);
+int nerfhip_cull_compact(const uint8_t* hit, const float* rays, const float* t0, const float* t1, int64_t n, int32_t* slot,
+                         int32_t* index, float* rays_out, int32_t* n_hit, void* workspace, nerfhip_stream_t stream);
+int nerfhip_cull_scatter(const int32_t* slot, int64_t n, int64_t n_compact, int white_back, const float* rgb, float* rgb_out,
+                         const float* depth, float* depth_out, const float* opacity_a, float* opacity_a_out, const float* opacity_b,
+                         float* opacity_b_out, nerfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,15 @@ SIGNATURES = {
     "nerfhip_png_code_lengths": [_c_void_p, _int, _int, _c_void_p],
     "nerfhip_inflate": [_c_void_p, _c_void_p, _i64, _int, _c_void_p, _i64, _i64, _c_void_p, _c_void_p],
     "nerfhip_inflate_host": [_c_void_p, _c_void_p, _i64, _int, _c_void_p, _i64, _i64, _c_void_p],
+    "nerfhip_occupancy_workspace_bytes": [_int],
+    "nerfhip_occupancy_build": [_c_void_p, _int, _f32, _int, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_cull_rays": [_c_void_p, _i64, _c_void_p, _int, ctypes.POINTER(_f32), _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_cull_rays_host": [_c_void_p, _i64, _c_void_p, _int, ctypes.POINTER(_f32), _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_cull_compact_workspace_bytes": [_i64],
+    "nerfhip_cull_compact": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                             _c_void_p],
+    "nerfhip_cull_scatter": [_c_void_p, _i64, _i64, _int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                             _c_void_p, _c_void_p],
 }
 
 
@@ -215,7 +224,8 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_ssim_workspace_bytes": ctypes.c_size_t,
              "nerfhip_depth_colormap_workspace_bytes": ctypes.c_size_t, "nerfhip_gif_workspace_bytes": ctypes.c_size_t,
              "nerfhip_gif_data_stride": ctypes.c_size_t, "nerfhip_vol_workspace_bytes": ctypes.c_size_t,
-             "nerfhip_png_workspace_bytes": ctypes.c_size_t, "nerfhip_png_data_stride": ctypes.c_size_t}
+             "nerfhip_png_workspace_bytes": ctypes.c_size_t, "nerfhip_png_data_stride": ctypes.c_size_t,
+             "nerfhip_occupancy_workspace_bytes": ctypes.c_size_t, "nerfhip_cull_compact_workspace_bytes": ctypes.c_size_t}
 
 _lib = None
 

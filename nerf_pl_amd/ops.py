@@ -1580,3 +1580,140 @@ def inflate_batch(streams, out_bytes, device, return_status=False, names=None):
         return out, host
     _inflate_status_error("nerfhip_inflate", names, host)
     return out
+
+
+# ------------------------------------------------------------ skipping empty space at eval (csrc/occupancy.hip)
+OCCUPANCY_MAX_N = 1025
+
+
+def occupancy_words(M):
+    """int32 words of the bitfield of an M^3-cell grid."""
+    return (int(M) ** 3 + 31) // 32
+
+
+def _ranges_arg(what, ranges):
+    """((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi)) -> the 6 host floats of the C call."""
+    flat = [float(v) for r in ranges for v in r]
+    if len(flat) != 6:
+        raise ValueError("%s: ranges must be three (lo, hi) pairs, got %r" % (what, ranges))
+    return (ctypes.c_float * 6)(*flat)
+
+
+def _require_dev(what, name, t, dtype, shape_tail=None):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: %s needs %s on the device (no CPU fallback)" % (what, name))
+    if t.dtype != dtype or (shape_tail is not None and tuple(t.shape[1:]) != shape_tail):
+        raise NerfHipError("%s: %s must be %s (n%s), got %s %s" % (what, name, dtype, "".join(", %d" % s for s in shape_tail or ()),
+                                                                    tuple(t.shape), t.dtype))
+    return _c(t)
+
+
+def _same_device(what, *tensors):
+    """the tensors of one call live on one GPU: a pointer of another device would be an illegal access, not an error"""
+    devs = {t.device for t in tensors if t is not None}
+    if len(devs) > 1:
+        raise NerfHipError("%s: tensors of one call live on different GPUs (%s)" % (what, ", ".join(sorted(str(d) for d in devs))))
+
+
+@device_guard
+def occupancy_build(sigma, threshold=0.0, dilate=1):
+    """nerfhip_occupancy_build: sigma (N, N, N) fp32 on the device, indexed [iy, ix, iz] (grid.sigma_grid) -> the bitfield of its
+    (N-1)^3 cells, (ceil((N-1)^3 / 32),) int32 on the device."""
+    sigma = _require_dev("occupancy_build", "sigma", sigma, torch.float32)
+    if sigma.dim() != 3 or len(set(sigma.shape)) != 1 or not 2 <= sigma.shape[0] <= OCCUPANCY_MAX_N:
+        raise ValueError("occupancy_build: sigma must be (N, N, N) with 2 <= N <= %d, got %s" % (OCCUPANCY_MAX_N, tuple(sigma.shape)))
+    if int(dilate) < 0:
+        raise ValueError("occupancy_build: dilate must be >= 0, got %r" % (dilate,))
+    lib = _lib.load()
+    N = sigma.shape[0]
+    words = torch.empty(occupancy_words(N - 1), device=sigma.device, dtype=torch.int32)
+    ws = torch.empty(lib.nerfhip_occupancy_workspace_bytes(N), device=sigma.device, dtype=torch.uint8)
+    check(lib.nerfhip_occupancy_build(ptr(sigma), N, float(threshold), int(dilate), ptr(words), ptr(ws), stream_ptr()),
+          "nerfhip_occupancy_build")
+    return words
+
+
+def _cull_grid_args(what, words, M, ranges):
+    """`words` (a tensor or an array) must hold the whole grid: a short one would be an out-of-bounds read, not an error."""
+    M = int(M)
+    have = words.numel() if torch.is_tensor(words) else words.size
+    if 1 <= M < OCCUPANCY_MAX_N and have < occupancy_words(M):
+        raise ValueError("%s: %d words for a grid of %d^3 cells (needs %d)" % (what, have, M, occupancy_words(M)))
+    return M, _ranges_arg(what, ranges)
+
+
+@device_guard
+def cull_rays(rays, words, M, ranges):
+    """nerfhip_cull_rays: rays (n, 8) fp32 against the bitfield `words` of an M^3 grid over `ranges` -> (hit (n,) uint8,
+    t0 (n,), t1 (n,)) on the device."""
+    rays = _require_dev("cull_rays", "rays", rays, torch.float32, (8,))
+    words = _require_dev("cull_rays", "words", words, torch.int32)
+    _same_device("cull_rays", rays, words)
+    M, rg = _cull_grid_args("cull_rays", words, M, ranges)
+    n = rays.shape[0]
+    hit = torch.empty(n, device=rays.device, dtype=torch.uint8)
+    t0 = torch.empty(n, device=rays.device, dtype=torch.float32)
+    t1 = torch.empty(n, device=rays.device, dtype=torch.float32)
+    check(_lib.load().nerfhip_cull_rays(ptr(rays), n, ptr(words), M, rg, ptr(hit), ptr(t0), ptr(t1), stream_ptr()), "nerfhip_cull_rays")
+    return hit, t0, t1
+
+
+def cull_rays_host(rays, words, M, ranges):
+    """nerfhip_cull_rays_host (host, no GPU): numpy rays (n, 8) float32 and int32 words -> numpy (hit, t0, t1), by the kernel's
+    own per-ray routine.  For tests of the traversal on a machine without a GPU."""
+    import numpy as np
+    rays = np.ascontiguousarray(rays, np.float32)
+    words = np.ascontiguousarray(words, np.int32)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("cull_rays_host: rays must be (n, 8), got %s" % (rays.shape,))
+    M, rg = _cull_grid_args("cull_rays_host", words, M, ranges)
+    n = rays.shape[0]
+    hit, t0, t1 = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    check(_lib.load().nerfhip_cull_rays_host(rays.ctypes.data, n, words.ctypes.data, M, rg, hit.ctypes.data, t0.ctypes.data,
+                                             t1.ctypes.data), "nerfhip_cull_rays_host")
+    return hit, t0, t1
+
+
+@device_guard
+def cull_compact(hit, rays, t0=None, t1=None):
+    """nerfhip_cull_compact: -> (slot (n,) int32, index (n,) int32, rays_out (n, 8), n_hit (1,) int32), all on the device and
+    sized for every ray hitting: the first n_hit rows of index and rays_out are written.  t0 / t1 None: the rows keep their own
+    near / far.  No host synchronisation."""
+    rays = _require_dev("cull_compact", "rays", rays, torch.float32, (8,))
+    hit = _require_dev("cull_compact", "hit", hit, torch.uint8, ())
+    t0 = None if t0 is None else _require_dev("cull_compact", "t0", t0, torch.float32, ())
+    t1 = None if t1 is None else _require_dev("cull_compact", "t1", t1, torch.float32, ())
+    n = rays.shape[0]
+    _same_device("cull_compact", rays, hit, t0, t1)
+    if any(t.shape[0] != n for t in (hit, t0, t1) if t is not None):
+        raise ValueError("cull_compact: hit, t0, t1 must have one entry per ray (%d)" % n)
+    dev = rays.device
+    lib = _lib.load()
+    slot = torch.empty(n, device=dev, dtype=torch.int32)
+    index = torch.empty(n, device=dev, dtype=torch.int32)
+    rays_out = torch.empty(n, 8, device=dev, dtype=torch.float32)
+    n_hit = torch.empty(1, device=dev, dtype=torch.int32)
+    ws = torch.empty(lib.nerfhip_cull_compact_workspace_bytes(n), device=dev, dtype=torch.uint8)
+    check(lib.nerfhip_cull_compact(ptr(hit), ptr(rays), ptr(t0), ptr(t1), n, ptr(slot), ptr(index), ptr(rays_out), ptr(n_hit), ptr(ws),
+                                   stream_ptr()), "nerfhip_cull_compact")
+    return slot, index, rays_out, n_hit
+
+
+@device_guard
+def cull_scatter(slot, white_back, rgb=None, depth=None, opacity_a=None, opacity_b=None):
+    """nerfhip_cull_scatter: compact values (n_compact rows each; any may be None) -> full-size tensors of slot.shape[0] rows in
+    the same order (None stays None): row i is the compact row slot[i], or the background (rgb: 1.0 with white_back, else 0.0;
+    the others 0.0) where slot[i] is -1."""
+    slot = _require_dev("cull_scatter", "slot", slot, torch.int32, ())
+    n = slot.shape[0]
+    src = [None if t is None else _require_dev("cull_scatter", name, t, torch.float32, tail)
+           for name, t, tail in (("rgb", rgb, (3,)), ("depth", depth, ()), ("opacity_a", opacity_a, ()), ("opacity_b", opacity_b, ()))]
+    _same_device("cull_scatter", slot, *src)
+    rows = {t.shape[0] for t in src if t is not None}
+    if len(rows) > 1 or (rows and max(rows) > n):
+        raise ValueError("cull_scatter: the compact tensors must have the same number of rows, at most %d; got %s" % (n, sorted(rows)))
+    n_compact = rows.pop() if rows else 0
+    out = [None if t is None else torch.empty((n,) + tuple(t.shape[1:]), device=slot.device, dtype=torch.float32) for t in src]
+    args = [p for s, o in zip(src, out) for p in (ptr(s), ptr(o))]
+    check(_lib.load().nerfhip_cull_scatter(ptr(slot), n, n_compact, int(bool(white_back)), *args, stream_ptr()), "nerfhip_cull_scatter")
+    return tuple(out)
