@@ -856,6 +856,32 @@ int nerfhip_cull_scatter(const int32_t* slot, int64_t n, int64_t n_compact, int 
                          const float* depth, float* depth_out, const float* opacity_a, float* opacity_a_out, const float* opacity_b,
                          float* opacity_b_out, nerfhip_stream_t stream);
 
+/* ---- epoch sampling  (train.py:89-94 DataLoader(shuffle=True): every ray once per epoch, shuffled) ------------
+ * The shuffle is a keyed bijection on [0, n) evaluated per position (a public function: csrc/epoch_core.h states it exactly):
+ * a six-round alternating Feistel network over max(2, ceil(log2 n)) bits with murmur3's 32-bit finaliser as the round function,
+ * round keys expanded from (seed, epoch) by splitmix64, cycle-walked into [0, n).  1 <= n <= 2^40.
+ * Ranks follow torch's DistributedSampler: rank r of `world` owns n_rank = ceil(n / world) positions and its j-th id is
+ * perm((j world + r) mod n); all ranks use the same (seed, epoch).
+ *
+ * epoch_ids_host: HOST function — host pointers only, no GPU: out[i] = the (first + i)-th id of the rank, i < count.
+ * epoch_ids: the same into device memory, one thread per id, the same bits.
+ * epoch_batch: ONE launch = batch `cursor` of epoch `epoch` of the rank: the ids of positions [cursor B, cursor B + rows),
+ * rows = min(B, n_rank - cursor B), their rays (rows,8) and colours (rows,3) exactly as nerfhip_sample_batch makes them for
+ * those ids (batch->rays / batch->rgbs hold B rows; the rows past `rows` are left alone), and the ids themselves into
+ * ids_or_null.  state: a DEVICE buffer of 4 x uint64 {seed, epoch, cursor, arrival ticket (0)}; the launch reads seed, epoch and
+ * cursor from it and its last workgroup writes the next cursor — or cursor 0 and epoch + 1 after the epoch's last batch, which is
+ * batch ceil(n_rank / B) - 1, or with drop_last batch floor(n_rank / B) - 1 (the tail of n_rank mod B positions is then never
+ * served) — so hipGraph replays of one captured call walk through batches and epochs.  B <= 2^30; drop_last needs B <= n_rank.
+ *
+ * Every entry returns NERFHIP_E_BADARG for n < 1, n > 2^40, world < 1, rank outside [0, world), B < 1, first < 0, count < 0,
+ * first + count > n_rank, null pointers (count > 0) and misaligned ones (int64 / uint64: 8 bytes; rays: 16; floats: 4).         */
+int nerfhip_epoch_ids_host(uint64_t seed, uint64_t epoch, int64_t n, int rank, int world, int64_t first, int64_t count,
+                           int64_t* out);
+int nerfhip_epoch_ids(uint64_t seed, uint64_t epoch, int64_t n, int rank, int world, int64_t first, int64_t count,
+                      int64_t* out_dev, nerfhip_stream_t stream);
+int nerfhip_epoch_batch(const nerfhip_ray_batch* batch, int64_t n_pixels, int64_t B, int rank, int world, int drop_last,
+                        uint64_t* state, int64_t* ids_or_null, nerfhip_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,9 @@ SIGNATURES = {
                              _c_void_p],
     "nerfhip_cull_scatter": [_c_void_p, _i64, _i64, _int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                              _c_void_p, _c_void_p],
+    "nerfhip_epoch_ids_host": [ctypes.c_uint64, ctypes.c_uint64, _i64, _int, _int, _i64, _i64, _c_void_p],
+    "nerfhip_epoch_ids": [ctypes.c_uint64, ctypes.c_uint64, _i64, _int, _int, _i64, _i64, _c_void_p, _c_void_p],
+    "nerfhip_epoch_batch": [_c_void_p, _i64, _i64, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p],
 }
 
 

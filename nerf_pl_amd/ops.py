@@ -1717,3 +1717,39 @@ def cull_scatter(slot, white_back, rgb=None, depth=None, opacity_a=None, opacity
     args = [p for s, o in zip(src, out) for p in (ptr(s), ptr(o))]
     check(_lib.load().nerfhip_cull_scatter(ptr(slot), n, n_compact, int(bool(white_back)), *args, stream_ptr()), "nerfhip_cull_scatter")
     return tuple(out)
+
+
+# ---- epoch sampling (csrc/epoch.hip) -----------------------------------------------------------------------------
+def _u64(v):
+    return int(v) & ((1 << 64) - 1)
+
+
+def epoch_share(n, world=1):
+    """Positions a rank owns per epoch: ceil(n / world) (torch's DistributedSampler without drop_last)."""
+    return (int(n) + int(world) - 1) // int(world)
+
+
+def epoch_ids_host(seed, epoch, n, rank=0, world=1, first=0, count=None):
+    """nerfhip_epoch_ids_host (host, no GPU): the ids of positions [first, first + count) of `rank`'s share of epoch `epoch` under
+    `seed`, as an int64 numpy array, by the kernel's own per-id routine.  count None: up to the end of the share."""
+    import numpy as np
+    if count is None:
+        count = epoch_share(n, world) - int(first)
+    out = np.empty(max(int(count), 0), np.int64)
+    check(_lib.load().nerfhip_epoch_ids_host(_u64(seed), _u64(epoch), int(n), int(rank), int(world), int(first), int(count),
+                                             out.ctypes.data if out.size else None), "nerfhip_epoch_ids_host")
+    return out
+
+
+def epoch_ids(seed, epoch, n, device, rank=0, world=1, first=0, count=None):
+    """nerfhip_epoch_ids: the same ids as an int64 tensor on `device`, one thread per id."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: epoch_ids got device %s (epoch_ids_host is the host entry)" % device)
+    if count is None:
+        count = epoch_share(n, world) - int(first)
+    with torch.cuda.device(device):
+        out = torch.empty(max(int(count), 0), device=device, dtype=torch.int64)
+        check(_lib.load().nerfhip_epoch_ids(_u64(seed), _u64(epoch), int(n), int(rank), int(world), int(first), int(count), ptr(out),
+                                            stream_ptr()), "nerfhip_epoch_ids")
+    return out

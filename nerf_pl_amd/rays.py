@@ -1,9 +1,13 @@
 """`datasets/ray_utils.py` of the reference on the device, plus a device-resident ray/pixel store.
 
 `get_ray_directions`, `get_rays`, `get_ndc_rays` keep the reference signatures (ray_utils.py:5-94) and run as single HIP
-launches; `RayStore` replaces the reference's CPU-side "precompute every ray of the dataset + DataLoader" pattern
-(blender.py:42-69,81-84, train.py:89-94): it keeps only the camera poses and the pixel colours in HBM and regenerates
-each batch's rays from 8-byte pixel ids (`nerfhip_gen_rays`), so a training batch never crosses PCIe."""
+launches; `RayStore` replaces the reference's CPU-side "precompute every ray of the dataset" pattern (blender.py:42-69,81-84):
+it keeps only the camera poses and the pixel colours in HBM and regenerates each batch's rays from 8-byte pixel ids
+(`nerfhip_gen_rays`), so a training batch never crosses PCIe.  Two ways to pick a batch's pixels: `RayStore.sample` draws them
+with torch.randint — independently, WITH replacement, which is not what the reference's DataLoader does — and `EpochSampler`
+(`RayStore.epoch_sampler`) is that DataLoader (train.py:89-94, shuffle=True): every ray once per epoch in a shuffled order."""
+import ctypes
+
 import torch
 
 from . import _lib
@@ -127,3 +131,155 @@ class RayStore:
         hw = self.H * self.W
         return gen_rays(self.poses, self.H, self.W, self.focal, self.near, self.far, first_pixel=i * hw, n=hw,
                         use_ndc=self.use_ndc, ndc_near_plane=self.ndc_near_plane)
+
+    def epoch_sampler(self, batch_size, seed=None, rank=0, world=1, last="partial"):
+        """The reference's DataLoader(shuffle=True) over this store: see EpochSampler."""
+        return EpochSampler(self, batch_size, seed=seed, rank=rank, world=world, last=last)
+
+
+def _epoch_plan(n, batch_size, world, last):
+    """(positions of one rank per epoch, batches per epoch, rows of the last batch) — host arithmetic only."""
+    n, B, world = int(n), int(batch_size), int(world)
+    if n < 1 or B < 1 or world < 1:
+        raise ValueError("epoch sampling needs n >= 1, batch_size >= 1, world >= 1")
+    if last not in ("partial", "drop"):
+        raise ValueError("last must be 'partial' (the DataLoader's drop_last=False) or 'drop'")
+    share = (n + world - 1) // world
+    if last == "drop":
+        if B > share:
+            raise ValueError("last='drop' with batch_size %d above the rank's %d rays leaves no batch" % (B, share))
+        return share, share // B, B
+    steps = (share + B - 1) // B
+    return share, steps, share - (steps - 1) * B
+
+
+class EpochSampler:
+    """Epoch sampling as the reference's `DataLoader(train_dataset, shuffle=True, batch_size=B)` does it (train.py:89-94): every
+    ray of the store once per epoch in a fresh shuffled order, the last batch partial (`last="partial"`) or skipped (`"drop"`:
+    a tail of fewer than B rays, a different one every epoch).  With `world` > 1 the ranks split an epoch as torch's
+    DistributedSampler does: rank r serves ceil(n / world) positions, r, r + world, ... wrapping past n.
+
+    The shuffle is a keyed permutation evaluated per ray (csrc/epoch_core.h) from (seed, epoch): no index tensor, no host work per
+    step, and no draw from any torch generator — the step's Philox stream keeps only the render draws, as in the reference, whose
+    RandomSampler shuffles with a private CPU generator.  `seed=None` takes torch.initial_seed() (a read).  One launch
+    (nerfhip_epoch_batch) makes a batch; epoch and cursor live in device memory (`state`) and the launch advances them, so a
+    captured `sample` walks through the epochs on replay.
+
+    Host mirror: `epoch`, `cursor`, `steps_per_epoch`, `epoch_done` (true after the call that served an epoch's last batch) are
+    counted on the host — one per eager `sample()`, one per `replayed()` for a captured one — and never read the device."""
+
+    def __init__(self, store, batch_size, seed=None, rank=0, world=1, last="partial"):
+        self.store = store
+        self.batch_size, self.rank, self.world, self.last = int(batch_size), int(rank), int(world), last
+        if not 0 <= self.rank < self.world:
+            raise ValueError("rank must lie in [0, world)")
+        self.n_rank, self.steps_per_epoch, self.tail_rows = _epoch_plan(store.n_pixels, batch_size, world, last)
+        self.seed = (int(torch.initial_seed()) if seed is None else int(seed)) & ((1 << 64) - 1)
+        self.epoch, self.cursor, self.epoch_done = 0, 0, False
+        self.state = None              # device {seed, epoch, cursor, arrival ticket}: made at the first launch
+        self._uploaded = False
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    # ---- host mirror ----
+    def _advance(self, times=1):
+        for _ in range(int(times)):
+            self.cursor += 1
+            self.epoch_done = self.cursor >= self.steps_per_epoch
+            if self.epoch_done:
+                self.cursor = 0
+                self.epoch += 1
+
+    def replayed(self, times=1):
+        """Tell the mirror that a captured `sample()` launch was replayed `times` times (GraphedTrainStep calls this itself)."""
+        self._advance(times)
+
+    def source(self, step_draws=None, pack_models=None):
+        """`sample` with its arguments bound, as a `batch_source` for GraphedTrainStep (which tells it of every replay)."""
+        def next_batch():
+            return self.sample(step_draws=step_draws, pack_models=pack_models)
+        next_batch.replayed = self.replayed
+        return next_batch
+
+    def rows(self, cursor=None):
+        """Rows of batch `cursor` (default: the next one)."""
+        c = self.cursor if cursor is None else int(cursor)
+        return self.tail_rows if c == self.steps_per_epoch - 1 else self.batch_size
+
+    def state_dict(self):
+        return {"seed": self.seed, "epoch": self.epoch, "cursor": self.cursor, "rank": self.rank, "world": self.world,
+                "batch_size": self.batch_size, "last": self.last}
+
+    def load_state_dict(self, sd):
+        """Continue inside the epoch the saved run was in.  The layout (rank, world, batch_size, last) must be the saved one: a
+        cursor means nothing under another."""
+        for k in ("rank", "world", "batch_size", "last"):
+            if sd[k] != getattr(self, k):
+                raise ValueError("EpochSampler.load_state_dict: saved %s=%r, this sampler has %r" % (k, sd[k], getattr(self, k)))
+        if not 0 <= int(sd["cursor"]) < self.steps_per_epoch or int(sd["epoch"]) < 0:
+            raise ValueError("EpochSampler.load_state_dict: cursor / epoch out of range")
+        self.seed, self.epoch, self.cursor = int(sd["seed"]) & ((1 << 64) - 1), int(sd["epoch"]), int(sd["cursor"])
+        self.epoch_done = False
+        self._uploaded = False
+
+    def _upload(self):
+        dev = self.store.poses.device
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.NerfHipError("EpochSampler: the device state must be loaded before a capture starts — call sample() or "
+                                    "prepare() once outside it")
+        if self.state is None:
+            self.state = torch.zeros(4, device=dev, dtype=torch.int64)
+        wrap = lambda v: v - (1 << 64) if v >= (1 << 63) else v          # uint64 bit patterns in an int64 tensor
+        self.state.copy_(torch.tensor([wrap(self.seed), wrap(self.epoch), self.cursor, 0], dtype=torch.int64))
+        self._uploaded = True
+
+    def prepare(self):
+        """Load the device state from the mirror if it is not there yet (not during a capture).  sample() does it itself."""
+        if not self._uploaded:
+            self._upload()
+        return self
+
+    def sample(self, step_draws=None, pack_models=None, return_ids=False):
+        """The next batch of the epoch in ONE launch: the batch dict of RayStore.sample ({'rays', 'rgbs'}, 'ids' on request).  The
+        epoch's last batch has `rows()` < batch_size rows under last="partial".
+        step_draws / pack_models as in RayStore.sample, made by one more launch (draws.draws on the step's specs without the
+        leading randint): batch['draws'] and batch['packed'] are what NeRFSystem.training_step consumes."""
+        st = self.store
+        dev = st.poses.device
+        B = self.batch_size
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing and self.last == "partial" and self.n_rank % B != 0:
+            raise _lib.NerfHipError("EpochSampler: a captured graph has one batch shape, but last='partial' ends every epoch with a "
+                                    "batch of %d rows instead of %d; use last='drop' or a batch size dividing %d"
+                                    % (self.tail_rows, B, self.n_rank))
+        with torch.cuda.device(dev):
+            self.prepare()
+            rows = B if capturing else self.rows()
+            rays = torch.empty(B, 8, device=dev, dtype=torch.float32)
+            rgbs = torch.empty(B, 3, device=dev, dtype=torch.float32)
+            ids = torch.empty(B, device=dev, dtype=torch.int64) if return_ids else None
+            rb = _lib.RayBatch()
+            rb.c2w, rb.rgbs_all, rb.rays, rb.rgbs = st.poses.data_ptr(), st.rgbs.data_ptr(), rays.data_ptr(), rgbs.data_ptr()
+            rb.H, rb.W, rb.focal, rb.near, rb.far = st.H, st.W, st.focal, st.near, st.far
+            rb.use_ndc, rb.ndc_near_plane = int(st.use_ndc), st.ndc_near_plane
+            check(_lib.load().nerfhip_epoch_batch(ctypes.addressof(rb), st.n_pixels, B, self.rank, self.world,
+                                                  int(self.last == "drop"), ptr(self.state), ptr(ids), stream_ptr()),
+                  "nerfhip_epoch_batch")
+        if not capturing:                  # a captured launch runs when it is replayed: replayed() counts those
+            self._advance()
+        batch = {"rays": rays[:rows], "rgbs": rgbs[:rows]}
+        if return_ids:
+            batch["ids"] = ids[:rows]
+        if step_draws is not None:
+            from . import draws as D
+            S, N, perturb, noise_std = step_draws
+            keys, specs = D.step_specs(rows, int(S), int(N), float(perturb), float(noise_std))
+            outs = D.draws(specs, dev, None, batch=None, pack=pack_models)
+            batch["draws"] = {k: t for k, t in zip(keys, outs) if t is not None}
+        elif pack_models is not None:
+            from . import ops
+            ops.pack_models_train(*pack_models)
+        if pack_models is not None:
+            batch["packed"] = pack_ticket(*pack_models)
+        return batch

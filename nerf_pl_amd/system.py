@@ -212,6 +212,30 @@ def fit(system, batches, grad_sync=None, steps=None):
     return losses
 
 
+def fit_epochs(system, sampler, num_epochs, grad_sync=None):
+    """`fit` by epochs, as Trainer.fit runs the reference (train.py:89-94, --num_epochs): batches come from a rays.EpochSampler
+    until it reports the epoch's last one, then the scheduler steps — once per epoch, as Lightning calls it.  Returns the
+    per-epoch lists of losses.  A sampler resumed mid-epoch (load_state_dict) finishes that epoch first."""
+    (opt,), (scheduler,) = system.configure_optimizers()
+    epochs = []
+    for _ in range(int(num_epochs)):
+        losses = []
+        done = False
+        while not done:
+            batch = sampler.sample()
+            done = sampler.epoch_done
+            out = system.training_step(batch, len(losses))
+            opt.zero_grad(set_to_none=True)
+            out['loss'].backward()
+            if grad_sync is not None:
+                grad_sync.sync()
+            opt.step()
+            losses.append(out['loss'].detach())
+        scheduler.step()
+        epochs.append(losses)
+    return epochs
+
+
 class GraphedTrainStep:
     """One full training step (training_step -> backward -> [gradient all-reduce] -> optimizer.step) replayed as
     hipGraphs (`torch.cuda.CUDAGraph`).
@@ -375,6 +399,11 @@ class GraphedTrainStep:
         self.graph.replay()
         if ds is not None:
             ds.after_replay()
+        # a batch source that counts its launches on the host (rays.EpochSampler's sample / source()) hears of the replay: a
+        # `replayed` attribute of the callable or of the object it is bound to.  Any other callable has none: nothing happens
+        replayed = getattr(self.batch_source, "replayed", None) or getattr(getattr(self.batch_source, "__self__", None), "replayed", None)
+        if replayed is not None:
+            replayed()
         if self.graph_opt is not None:
             self.grad_sync.sync()
             self.graph_opt.replay()
