@@ -882,6 +882,51 @@ int nerfhip_epoch_ids(uint64_t seed, uint64_t epoch, int64_t n, int rank, int wo
 int nerfhip_epoch_batch(const nerfhip_ray_batch* batch, int64_t n_pixels, int64_t B, int rank, int world, int drop_last,
                         uint64_t* state, int64_t* ids_or_null, nerfhip_stream_t stream);
 
+/* ---- rendering the baked RGBA volume  (README_Unity.md "VolumeRender": the .vol file as a Texture3D) -----------
+ * Opt-in and beside everything else: the N^3 RGBA8 lattice of a .vol file kept on the device in bricks, the bitfield of its
+ * occupied bricks, and a ray march through both.  The reference's consumer is a Unity shader; the semantics here are this
+ * library's own and csrc/baked_core.h states them exactly.  Nothing is allocated, nothing synchronises, no runtime object is
+ * created.  2 <= N <= 1625 (N^3 < 2^32, the file's index type).
+ *
+ * The bricked volume (a public format).  Lattice point (iy, ix, iz) — point i = iy N^2 + ix N + iz of the file, the element
+ * [iy, ix, iz] of volume.read_vol's array — lies in brick (by NB + bx) NB + bz, b* = i* >> 3, NB = ceil(N / 8), at local index
+ * ((iy & 7) 8 + (ix & 7)) 8 + (iz & 7).  A brick is 512 points of 4 bytes, R G B A in memory order, 2 KiB; points past the lattice
+ * are zero; the volume is baked_bytes(N) = NB^3 2048 bytes (0 for a refused N), 16-byte aligned.  A pure permutation, no apron.
+ *
+ * baked_scatter: clears `data`, then stores the K records (K,2) int32 = [i, R << 24 | G << 16 | B << 8 | A] of a .vol file
+ * (volume.vol_records / export_vol / write_vol; 8-byte aligned; the indices distinct).  A record with i >= N^3 is not stored
+ * and is counted into *n_bad, one int32 on the DEVICE that the call zeroes first.  baked_from_dense: the same volume from the
+ * dense lattice rgba (N,N,N,4) uint8, 4-byte aligned.  One thread per record or point.
+ *
+ * baked_bricks: the (N-1)^3 cells in bricks of 8^3 cells, MB = ceil((N-1) / 8) per axis.  Cell brick (by, bx, bz) is occupied iff
+ * a lattice point with every index in [8 b, 8 b + 8], clipped to [0, N-1], has A > 0: every corner of every cell of the brick.
+ * words: ceil(MB^3 / 32) int32, brick c = (by MB + bx) MB + bz is bit c & 31 of word c >> 5, unused bits zero.
+ *
+ * baked_render: rays (n,8) = [o d near far], 16-byte aligned, d of any length; words_or_null: the bitfield, or null for "every
+ * brick occupied" — the outputs do not depend on it bit for bit, it only saves the gathers of empty bricks; ranges_host: 6 HOST
+ * floats x_lo x_hi y_lo y_hi z_lo z_hi, x along ix, y along iy, z along iz, the first and last lattice points on the ends.
+ * Per ray, in fp32: background (opacity 0, depth 0, rgb = white_back ? 1 : 0) for a non-finite value in any column, a zero
+ * direction or a ray that misses the box within [near, far]; else segments of step * cell world units from the box's entry to
+ * its exit, the last one cut short; per segment one alpha-weighted trilinear sample at the midpoint (a = sum w A / 255, colour
+ * = sum w A rgb / sum w A), alpha = 1 - (1 - a)^(segment length / cell) — the stored A belongs to a thickness of `cell`, as
+ * volume.export_vol makes it —, composited front to back: rgb (n,3), depth (n) = sum w t (unnormalised), opacity (n) = sum w;
+ * white_back adds 1 - opacity to rgb.  t_stop > 0 ends a ray after the first segment that leaves its transmittance below
+ * t_stop.  Any output may be null.  NERFHIP_E_BADARG before anything is launched or dereferenced: N outside [2, 1625], a range
+ * with lo >= hi or not finite, cell <= 0 or not finite, step outside [1/16, 8], t_stop outside [0, 1), a box whose diagonal is
+ * more than 2^20 segments long, n < 0 or > 2^30, null rays / data / ranges_host with n > 0.  n == 0 is success.
+ * baked_render_host: HOST function — host pointers only, no GPU, launches nothing: the same per-ray routine in a loop; its
+ * results differ from the device's by the two libraries' exp2f / log2f only.                                                     */
+size_t nerfhip_baked_bytes(int N);
+int nerfhip_baked_scatter(const int32_t* records, int64_t K, int N, uint8_t* data, int32_t* n_bad, nerfhip_stream_t stream);
+int nerfhip_baked_from_dense(const uint8_t* rgba, int N, uint8_t* data, nerfhip_stream_t stream);
+int nerfhip_baked_bricks(const uint8_t* data, int N, int32_t* words, nerfhip_stream_t stream);
+int nerfhip_baked_render(const float* rays, int64_t n, const uint8_t* data, const int32_t* words_or_null, int N,
+                         const float* ranges_host, float cell, float step, float t_stop, int white_back, float* rgb, float* depth,
+                         float* opacity, nerfhip_stream_t stream);
+int nerfhip_baked_render_host(const float* rays, int64_t n, const uint8_t* data, const int32_t* words_or_null, int N,
+                              const float* ranges_host, float cell, float step, float t_stop, int white_back, float* rgb,
+                              float* depth, float* opacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,8 @@ Drop-in use from the reference tree:
 All compute runs in hand-written HIP kernels behind a C ABI (include/nerfhip.h, libnerfhip.so);
 there is no CPU or eager fallback.
 
-Beyond the reference: `nerf_pl_amd.occupancy` (OccupancyGrid, CulledRenderer) skips empty space at eval, opt-in.
+Beyond the reference: `nerf_pl_amd.occupancy` (OccupancyGrid, CulledRenderer) skips empty space at eval, opt-in;
+`nerf_pl_amd.baked` (BakedVolume, BakedRenderer) renders the exported .vol lattice itself, without the network.
 """
 import os
 import sys

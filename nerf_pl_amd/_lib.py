@@ -169,6 +169,14 @@ SIGNATURES = {
     "nerfhip_epoch_ids_host": [ctypes.c_uint64, ctypes.c_uint64, _i64, _int, _int, _i64, _i64, _c_void_p],
     "nerfhip_epoch_ids": [ctypes.c_uint64, ctypes.c_uint64, _i64, _int, _int, _i64, _i64, _c_void_p, _c_void_p],
     "nerfhip_epoch_batch": [_c_void_p, _i64, _i64, _int, _int, _int, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_baked_bytes": [_int],
+    "nerfhip_baked_scatter": [_c_void_p, _i64, _int, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_baked_from_dense": [_c_void_p, _int, _c_void_p, _c_void_p],
+    "nerfhip_baked_bricks": [_c_void_p, _int, _c_void_p, _c_void_p],
+    "nerfhip_baked_render": [_c_void_p, _i64, _c_void_p, _c_void_p, _int, ctypes.POINTER(_f32), _f32, _f32, _f32, _int, _c_void_p,
+                             _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_baked_render_host": [_c_void_p, _i64, _c_void_p, _c_void_p, _int, ctypes.POINTER(_f32), _f32, _f32, _f32, _int, _c_void_p,
+                                  _c_void_p, _c_void_p],
 }
 
 
@@ -228,7 +236,8 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_depth_colormap_workspace_bytes": ctypes.c_size_t, "nerfhip_gif_workspace_bytes": ctypes.c_size_t,
              "nerfhip_gif_data_stride": ctypes.c_size_t, "nerfhip_vol_workspace_bytes": ctypes.c_size_t,
              "nerfhip_png_workspace_bytes": ctypes.c_size_t, "nerfhip_png_data_stride": ctypes.c_size_t,
-             "nerfhip_occupancy_workspace_bytes": ctypes.c_size_t, "nerfhip_cull_compact_workspace_bytes": ctypes.c_size_t}
+             "nerfhip_occupancy_workspace_bytes": ctypes.c_size_t, "nerfhip_cull_compact_workspace_bytes": ctypes.c_size_t,
+             "nerfhip_baked_bytes": ctypes.c_size_t}
 
 _lib = None
 

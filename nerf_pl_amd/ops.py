@@ -1753,3 +1753,126 @@ def epoch_ids(seed, epoch, n, device, rank=0, world=1, first=0, count=None):
         check(_lib.load().nerfhip_epoch_ids(_u64(seed), _u64(epoch), int(n), int(rank), int(world), int(first), int(count), ptr(out),
                                             stream_ptr()), "nerfhip_epoch_ids")
     return out
+
+
+# ---- rendering the baked RGBA volume (csrc/baked.hip) -------------------------------------------------------------
+BAKED_MAX_N = 1625
+
+
+def _baked_N(what, N):
+    N = int(N)
+    if not 2 <= N <= BAKED_MAX_N:
+        raise ValueError("%s: N must be in [2, %d] (N^3 < 2^32), got %d" % (what, BAKED_MAX_N, N))
+    return N
+
+
+def baked_bytes(N):
+    """Bytes of the bricked volume of an N^3 lattice: ceil(N / 8)^3 bricks of 2 KiB."""
+    return ((int(N) + 7) // 8) ** 3 * 2048
+
+
+def baked_brick_words(N):
+    """int32 words of the bitfield of the ceil((N - 1) / 8)^3 cell bricks of an N^3 lattice."""
+    return (((int(N) - 1 + 7) // 8) ** 3 + 31) // 32
+
+
+@device_guard
+def baked_scatter(records, N):
+    """nerfhip_baked_scatter: the (K, 2) int32 records of a .vol file (volume.vol_records / export_vol, on the device) -> the
+    bricked volume (baked_bytes(N),) uint8 of the N^3 lattice.  ValueError for a record whose index is >= N^3 (one host read of
+    the kernel's count), as volume.read_vol raises for the same file."""
+    N = _baked_N("baked_scatter", N)
+    records = _require_dev("baked_scatter", "records", records, torch.int32, (2,))
+    dev = records.device
+    data = torch.empty(baked_bytes(N), device=dev, dtype=torch.uint8)
+    n_bad = torch.empty(1, device=dev, dtype=torch.int32)
+    check(_lib.load().nerfhip_baked_scatter(ptr(records), records.shape[0], N, ptr(data), ptr(n_bad), stream_ptr()),
+          "nerfhip_baked_scatter")
+    bad = int(n_bad.item())
+    if bad:
+        raise ValueError("baked_scatter: %d records with an index outside the %d^3 lattice" % (bad, N))
+    return data
+
+
+@device_guard
+def baked_from_dense(rgba):
+    """nerfhip_baked_from_dense: a dense (N, N, N, 4) uint8 lattice on the device, indexed [iy, ix, iz] as volume.read_vol
+    returns it -> the bricked volume."""
+    if not torch.is_tensor(rgba) or not rgba.is_cuda:
+        raise NerfHipError("nerf_pl_amd runs on MI355X only: baked_from_dense needs rgba on the device (no CPU fallback)")
+    if rgba.dtype != torch.uint8 or rgba.dim() != 4 or rgba.shape[3] != 4 or len(set(rgba.shape[:3])) != 1:
+        raise ValueError("baked_from_dense: rgba must be (N, N, N, 4) uint8, got %s %s" % (tuple(rgba.shape), rgba.dtype))
+    N = _baked_N("baked_from_dense", rgba.shape[0])
+    rgba = _c(rgba)
+    data = torch.empty(baked_bytes(N), device=rgba.device, dtype=torch.uint8)
+    check(_lib.load().nerfhip_baked_from_dense(ptr(rgba), N, ptr(data), stream_ptr()), "nerfhip_baked_from_dense")
+    return data
+
+
+def _baked_data(what, data, N):
+    data = _require_dev(what, "data", data, torch.uint8, ())
+    if data.numel() != baked_bytes(N):
+        raise ValueError("%s: the bricked volume of a %d^3 lattice has %d bytes, got %d" % (what, N, baked_bytes(N), data.numel()))
+    return data
+
+
+@device_guard
+def baked_bricks(data, N):
+    """nerfhip_baked_bricks: the bricked volume -> the bitfield of its occupied cell bricks, (baked_brick_words(N),) int32."""
+    N = _baked_N("baked_bricks", N)
+    data = _baked_data("baked_bricks", data, N)
+    words = torch.empty(baked_brick_words(N), device=data.device, dtype=torch.int32)
+    check(_lib.load().nerfhip_baked_bricks(ptr(data), N, ptr(words), stream_ptr()), "nerfhip_baked_bricks")
+    return words
+
+
+@device_guard
+def baked_render(rays, data, bits, N, ranges, cell, step=0.5, t_stop=0.0, white_back=False):
+    """nerfhip_baked_render: rays (n, 8) fp32 marched through the bricked volume `data` of an N^3 lattice over `ranges` ->
+    (rgb (n, 3), depth (n,), opacity (n,)) on the device.  bits: the cell-brick bitfield, or None (no skipping; the same bits
+    of output)."""
+    N = _baked_N("baked_render", N)
+    rays = _require_dev("baked_render", "rays", rays, torch.float32, (8,))
+    data = _baked_data("baked_render", data, N)
+    if bits is not None:
+        bits = _require_dev("baked_render", "bits", bits, torch.int32, ())
+        if bits.numel() < baked_brick_words(N):
+            raise ValueError("baked_render: %d words for the bricks of a %d^3 lattice (needs %d)" % (bits.numel(), N, baked_brick_words(N)))
+    _same_device("baked_render", rays, data, bits)
+    rg = _ranges_arg("baked_render", ranges)
+    n = rays.shape[0]
+    rgb = torch.empty(n, 3, device=rays.device, dtype=torch.float32)
+    depth = torch.empty(n, device=rays.device, dtype=torch.float32)
+    opacity = torch.empty(n, device=rays.device, dtype=torch.float32)
+    check(_lib.load().nerfhip_baked_render(ptr(rays), n, ptr(data), ptr(bits), N, rg, float(cell), float(step), float(t_stop),
+                                           int(bool(white_back)), ptr(rgb), ptr(depth), ptr(opacity), stream_ptr()), "nerfhip_baked_render")
+    return rgb, depth, opacity
+
+
+def baked_render_host(rays, data, bits, N, ranges, cell, step=0.5, t_stop=0.0, white_back=False):
+    """nerfhip_baked_render_host (host, no GPU): numpy rays (n, 8) float32, the bricked volume as a uint8 array and the bitfield
+    as int32 words (or None) -> numpy (rgb, depth, opacity), by the kernel's own per-ray routine."""
+    import numpy as np
+    N = _baked_N("baked_render_host", N)
+    rays = np.ascontiguousarray(rays, np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("baked_render_host: rays must be (n, 8), got %s" % (rays.shape,))
+    data = np.ascontiguousarray(data, np.uint8).ravel()
+    if data.size != baked_bytes(N):
+        raise ValueError("baked_render_host: the bricked volume of a %d^3 lattice has %d bytes, got %d" % (N, baked_bytes(N), data.size))
+    if data.ctypes.data & 15:                             # the entry point wants the 16-byte alignment device buffers have
+        buf = np.empty(data.size + 16, np.uint8)
+        off = (-buf.ctypes.data) & 15
+        buf[off:off + data.size] = data
+        data = buf[off:off + data.size]
+    if bits is not None:
+        bits = np.ascontiguousarray(bits, np.int32)
+        if bits.size < baked_brick_words(N):
+            raise ValueError("baked_render_host: %d words for the bricks of a %d^3 lattice (needs %d)" % (bits.size, N, baked_brick_words(N)))
+    rg = _ranges_arg("baked_render_host", ranges)
+    n = rays.shape[0]
+    rgb, depth, opacity = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    check(_lib.load().nerfhip_baked_render_host(rays.ctypes.data, n, data.ctypes.data, None if bits is None else bits.ctypes.data, N, rg,
+                                                float(cell), float(step), float(t_stop), int(bool(white_back)), rgb.ctypes.data,
+                                                depth.ctypes.data, opacity.ctypes.data), "nerfhip_baked_render_host")
+    return rgb, depth, opacity
