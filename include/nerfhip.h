@@ -927,6 +927,81 @@ int nerfhip_baked_render_host(const float* rays, int64_t n, const uint8_t* data,
                               const float* ranges_host, float cell, float step, float t_stop, int white_back, float* rgb,
                               float* depth, float* opacity);
 
+/* ---- ray casting against a triangle mesh  (README "mixed reality": a virtual object in a NeRF render, z-ordered by NeRF's depth;
+ *      the consumer of extract_color_mesh's mesh) ------------------------------------------------------------------
+ * Opt-in and beside everything else: a hierarchy of boxes over a triangle mesh, the nearest hit of a ray in it, and two per-ray
+ * kernels that turn hits into pixels.  csrc/mesh_core.h states every routine exactly, and every entry point has a _host twin:
+ * a HOST function — host pointers only, no GPU, launches nothing — that runs the same routine in a loop and gives the same
+ * bits (plain fp32, IEEE division and square root, no libm).  Nothing is allocated, nothing synchronises, launches go to the
+ * caller's stream.  0 <= T <= 2^28 triangles, 0 <= V < 2^31 vertices, 0 <= n <= 2^30 rays.
+ *
+ * The mesh: vertices (V,3) fp32, triangles (T,3) int32.  A triangle with an index outside [0, V) or a non-finite coordinate is
+ * BAD: it is counted, gets an empty box and is never hit.
+ *
+ * The hierarchy (a public format).  The triangles are sorted by the int64 key  morton30 << 32 | t : the centroid
+ * ((v0 + v1) + v2) / 3 is quantised per axis to q = min(1023, trunc((c - lo) / (hi - lo) * 1024)) (0 where hi == lo) in the
+ * bounds [lo, hi] of the good triangles' vertices, and morton30 interleaves the three q with x in the highest bit of every
+ * triple; a bad triangle has morton30 = 2^30.  The keys are distinct, so the order does not depend on the sort.  Leaf j holds
+ * the sorted triangles [4j, 4j + 4) ∩ [0, T).  Level 0 has n_0 = ceil(T / 4) nodes, level k + 1 has ceil(n_k / 8), each
+ * bounding the 8 consecutive nodes [8i, 8i + 8) ∩ [0, n_k) of level k, up to a level of one node, the root.
+ * `boxes` is (mesh_bvh_nodes(T), 6) fp32 = [lo xyz, hi xyz], the levels concatenated from the leaves to the root; every box is
+ * the exact min / max of what it bounds (-0 below +0); a node that bounds bad triangles only has lo = +inf, hi = -inf.
+ * `tris` is (T, 12) fp32, 16-byte aligned, in sorted order: [v0 xyz, index, v1 xyz, 0, v2 xyz, 0], index the int32 bits of the
+ * original triangle number, -1 (and zero coordinates) for a bad triangle.  T = 0 is a valid hierarchy of 0 nodes.
+ * mesh_bvh_nodes: the number of nodes (0 for T outside [0, 2^28]).
+ *
+ * mesh_bvh_keys: `state`, 8 int32 on the DEVICE, is set first — [0] the number of bad triangles, [1] 0, [2..4] / [5..7] the
+ * bounds' lo / hi as order-preserving integers (csrc/mesh_core.h mesh_ordered) — then keys (T) int64, 8-byte aligned.
+ * mesh_bvh_boxes: sorted_keys (T) = the keys in ascending order (the caller sorts: torch.sort in ops.mesh_bvh_build) -> tris and
+ * boxes; one launch for the leaves and one per level above, at most 10, nothing handed between workgroups within a launch.  A
+ * sorted key whose low word is not in [0, T) is stored as a bad triangle.
+ *
+ * mesh_cast: rays (n,8) = [o d near far], 16-byte aligned, d of any length; one ray per lane.  tri (n) int32: the original
+ * number of the nearest triangle hit with near <= t <= far, -1 for a miss; t (n): the ray's own parameter (o + t d); b1, b2 (n):
+ * the barycentric weights of vertices 1 and 2.  A miss has t = b1 = b2 = 0.  A non-finite value in any column or a zero
+ * direction is a miss.  On an equal t the lower original number wins, so the result does not depend on the traversal.  The
+ * triangle test is the two-sided watertight one of Woop, Benthin and Wald (JCGT 2013) with the double fallback on a zero edge
+ * function.  t, b1, b2 may be null.  mesh_cast_host with brute != 0 ignores `boxes` (may be null) and tests every triangle.
+ *
+ * mesh_shade: rgb (n,3) = (b0 c0 + b1 c1 + b2 c2) (ambient + (1 - ambient) |n . d| / (|n| |d|)), c the vertex colours
+ * colors_or_null (V,3) uint8 / 255 (null: white), n the geometric normal of triangle tri[i]; `background` for tri < 0 (and for a
+ * tri >= T or a triangle naming a vertex outside [0, V)).  0 <= ambient <= 1.
+ *
+ * mixed_compose: a render (rgb_n (n,3), depth_n (n), opacity_n (n)) and a mesh layer (tri, t, rgb_m (n,3)) -> rgb, depth,
+ * opacity, mask_or_null (n) uint8.  mode 0 "ztest": s = opacity_n >= tau ? depth_n / opacity_n : +inf; the mesh wins iff
+ * tri >= 0 and t < s; the winner's rgb and depth pass through, opacity is 1 and mask 1 where the mesh wins.  mode 1 "clip" (the
+ * render was made with far = min(far, t) on hit rays and without a background): rgb = rgb_n + (1 - opacity_n) (hit ? rgb_m :
+ * background); on a hit depth = depth_n + (1 - opacity_n) t, opacity = 1, mask = 1; on a miss depth_n, opacity_n, 0.  tau > 0.
+ *
+ * NERFHIP_E_BADARG before anything is launched or dereferenced: T, V or n out of range, a null pointer that n > 0 (T > 0, V > 0
+ * for the mesh's arrays) would read or write, an unknown mode, ambient outside [0, 1], tau <= 0, a non-finite tau or
+ * background.  NERFHIP_E_ALIGN for rays (cast) or tris not 16-byte aligned, keys not 8-byte aligned, any other array not 4-byte
+ * aligned.  n == 0 (T == 0 for the build) is success.                                                                           */
+size_t nerfhip_mesh_bvh_nodes(int64_t T);
+int nerfhip_mesh_bvh_keys(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, int64_t* keys, int32_t* state,
+                          nerfhip_stream_t stream);
+int nerfhip_mesh_bvh_keys_host(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, int64_t* keys, int32_t* state);
+int nerfhip_mesh_bvh_boxes(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const int64_t* sorted_keys,
+                           float* tris, float* boxes, nerfhip_stream_t stream);
+int nerfhip_mesh_bvh_boxes_host(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const int64_t* sorted_keys,
+                                float* tris, float* boxes);
+int nerfhip_mesh_cast(const float* rays, int64_t n, const float* tris, const float* boxes, int64_t T, int32_t* tri, float* t,
+                      float* b1, float* b2, nerfhip_stream_t stream);
+int nerfhip_mesh_cast_host(const float* rays, int64_t n, const float* tris, const float* boxes, int64_t T, int brute, int32_t* tri,
+                           float* t, float* b1, float* b2);
+int nerfhip_mesh_shade(const float* rays, int64_t n, const int32_t* tri, const float* b1, const float* b2, const float* vertices,
+                       int64_t V, const int32_t* triangles, int64_t T, const uint8_t* colors_or_null, float ambient,
+                       float background, float* rgb, nerfhip_stream_t stream);
+int nerfhip_mesh_shade_host(const float* rays, int64_t n, const int32_t* tri, const float* b1, const float* b2,
+                            const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const uint8_t* colors_or_null,
+                            float ambient, float background, float* rgb);
+int nerfhip_mixed_compose(int mode, int64_t n, const float* rgb_n, const float* depth_n, const float* opacity_n, const int32_t* tri,
+                          const float* t, const float* rgb_m, float tau, float background, float* rgb, float* depth,
+                          float* opacity, uint8_t* mask_or_null, nerfhip_stream_t stream);
+int nerfhip_mixed_compose_host(int mode, int64_t n, const float* rgb_n, const float* depth_n, const float* opacity_n,
+                               const int32_t* tri, const float* t, const float* rgb_m, float tau, float background, float* rgb,
+                               float* depth, float* opacity, uint8_t* mask_or_null);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ All compute runs in hand-written HIP kernels behind a C ABI (include/nerfhip.h, 
 there is no CPU or eager fallback.
 
 Beyond the reference: `nerf_pl_amd.occupancy` (OccupancyGrid, CulledRenderer) skips empty space at eval, opt-in;
-`nerf_pl_amd.baked` (BakedVolume, BakedRenderer) renders the exported .vol lattice itself, without the network.
+`nerf_pl_amd.baked` (BakedVolume, BakedRenderer) renders the exported .vol lattice itself, without the network;
+`nerf_pl_amd.meshcast` (MeshBVH, MeshRenderer, MixedRenderer) ray-casts the extracted mesh and puts a mesh into any render.
 """
 import os
 import sys

@@ -177,6 +177,21 @@ SIGNATURES = {
                              _c_void_p, _c_void_p, _c_void_p],
     "nerfhip_baked_render_host": [_c_void_p, _i64, _c_void_p, _c_void_p, _int, ctypes.POINTER(_f32), _f32, _f32, _f32, _int, _c_void_p,
                                   _c_void_p, _c_void_p],
+    "nerfhip_mesh_bvh_nodes": [_i64],
+    "nerfhip_mesh_bvh_keys": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_bvh_keys_host": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p],
+    "nerfhip_mesh_bvh_boxes": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_bvh_boxes_host": [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_cast": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_cast_host": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _int, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mesh_shade": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _f32, _f32,
+                           _c_void_p, _c_void_p],
+    "nerfhip_mesh_shade_host": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _f32,
+                                _f32, _c_void_p],
+    "nerfhip_mixed_compose": [_int, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _f32, _f32, _c_void_p,
+                              _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "nerfhip_mixed_compose_host": [_int, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _f32, _f32, _c_void_p,
+                                   _c_void_p, _c_void_p, _c_void_p],
 }
 
 
@@ -237,7 +252,7 @@ _RESTYPES = {"nerfhip_error_string": ctypes.c_char_p, "nerfhip_torch_draw_increm
              "nerfhip_gif_data_stride": ctypes.c_size_t, "nerfhip_vol_workspace_bytes": ctypes.c_size_t,
              "nerfhip_png_workspace_bytes": ctypes.c_size_t, "nerfhip_png_data_stride": ctypes.c_size_t,
              "nerfhip_occupancy_workspace_bytes": ctypes.c_size_t, "nerfhip_cull_compact_workspace_bytes": ctypes.c_size_t,
-             "nerfhip_baked_bytes": ctypes.c_size_t}
+             "nerfhip_baked_bytes": ctypes.c_size_t, "nerfhip_mesh_bvh_nodes": ctypes.c_size_t}
 
 _lib = None
 

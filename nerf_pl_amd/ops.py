@@ -1876,3 +1876,262 @@ def baked_render_host(rays, data, bits, N, ranges, cell, step=0.5, t_stop=0.0, w
                                                 float(cell), float(step), float(t_stop), int(bool(white_back)), rgb.ctypes.data,
                                                 depth.ctypes.data, opacity.ctypes.data), "nerfhip_baked_render_host")
     return rgb, depth, opacity
+
+
+# ---- ray casting against a triangle mesh (csrc/meshcast.hip, DESIGN.md §20) -------------------------------------------------------
+MESH_MAX_TRIANGLES = 1 << 28
+MIXED_MODES = {"ztest": 0, "clip": 1}
+
+
+def mesh_bvh_levels(T):
+    """[(offset, nodes)] of the hierarchy's levels in `boxes`, from the leaves to the root (include/nerfhip.h): ceil(T / 4)
+    leaves, every level above an eighth (rounded up) of the one below.  [] for T = 0."""
+    T = int(T)
+    if not 0 <= T <= MESH_MAX_TRIANGLES:
+        raise ValueError("mesh_bvh_levels: T must be in [0, 2^28], got %d" % T)
+    out, off, n = [], 0, (T + 3) // 4
+    while n:
+        out.append((off, n))
+        off += n
+        n = (n + 7) // 8 if n > 1 else 0
+    return out
+
+
+def mesh_bvh_nodes(T):
+    """nerfhip_mesh_bvh_nodes: the rows of `boxes`."""
+    levels = mesh_bvh_levels(T)
+    return levels[-1][0] + levels[-1][1] if levels else 0
+
+
+def _mesh_arrays(what, vertices, triangles):
+    vertices = _require_dev(what, "vertices", vertices, torch.float32, (3,))
+    triangles = _require_dev(what, "triangles", triangles, torch.int32, (3,))
+    if vertices.dim() != 2 or triangles.dim() != 2:
+        raise NerfHipError("%s: vertices must be (V, 3) and triangles (T, 3)" % what)
+    if triangles.shape[0] > MESH_MAX_TRIANGLES:
+        raise ValueError("%s: at most 2^28 triangles, got %d" % (what, triangles.shape[0]))
+    _same_device(what, vertices, triangles)
+    return vertices, triangles
+
+
+@device_guard
+def mesh_bvh_build(vertices, triangles):
+    """nerfhip_mesh_bvh_keys, torch.sort, nerfhip_mesh_bvh_boxes: vertices (V, 3) fp32 and triangles (T, 3) int32 on the device ->
+    (tris (T, 12) fp32: the sorted triangles' vertices with their original numbers; boxes (mesh_bvh_nodes(T), 6) fp32; order (T,)
+    int32: the original number of every sorted triangle; n_bad (1,) int32 on the device: triangles with an index outside [0, V) or a
+    non-finite coordinate, which no cast returns).  The keys are distinct, so the sort decides nothing."""
+    vertices, triangles = _mesh_arrays("mesh_bvh_build", vertices, triangles)
+    dev = vertices.device
+    V, T = vertices.shape[0], triangles.shape[0]
+    lib = _lib.load()
+    keys = torch.empty(T, device=dev, dtype=torch.int64)
+    state = torch.empty(8, device=dev, dtype=torch.int32)
+    check(lib.nerfhip_mesh_bvh_keys(ptr(vertices), V, ptr(triangles), T, ptr(keys), ptr(state), stream_ptr()), "nerfhip_mesh_bvh_keys")
+    sorted_keys, _ = torch.sort(keys)
+    tris = torch.empty(T, 12, device=dev, dtype=torch.float32)
+    boxes = torch.empty(mesh_bvh_nodes(T), 6, device=dev, dtype=torch.float32)
+    check(lib.nerfhip_mesh_bvh_boxes(ptr(vertices), V, ptr(triangles), T, ptr(sorted_keys), ptr(tris), ptr(boxes), stream_ptr()),
+          "nerfhip_mesh_bvh_boxes")
+    order = (sorted_keys & 0xffffffff).to(torch.int32)
+    return tris, boxes, order, state[:1]
+
+
+def _np16(a, dtype):
+    """a C-contiguous numpy array of `dtype` whose data is 16-byte aligned, as device buffers are"""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype)
+    if a.ctypes.data & 15:
+        buf = np.empty(a.nbytes + 16, np.uint8)
+        off = (-buf.ctypes.data) & 15
+        out = buf[off:off + a.nbytes].view(dtype).reshape(a.shape)
+        out[...] = a
+        a = out
+    return a
+
+
+def _np_out(shape, dtype):
+    import numpy as np
+    return _np16(np.zeros(shape, dtype), dtype)
+
+
+def _mesh_arrays_host(what, vertices, triangles):
+    import numpy as np
+    vertices, triangles = _np16(vertices, np.float32), _np16(triangles, np.int32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or triangles.ndim != 2 or triangles.shape[1] != 3:
+        raise ValueError("%s: vertices must be (V, 3) and triangles (T, 3), got %s and %s" % (what, vertices.shape, triangles.shape))
+    return vertices, triangles
+
+
+def mesh_bvh_build_host(vertices, triangles):
+    """The _host twins of `mesh_bvh_build` with numpy's sort between them (host, no GPU): numpy in, numpy (tris, boxes, order,
+    n_bad (1,) int32) out, bit for bit what the device builds."""
+    import numpy as np
+    vertices, triangles = _mesh_arrays_host("mesh_bvh_build_host", vertices, triangles)
+    V, T = vertices.shape[0], triangles.shape[0]
+    lib = _lib.load()
+    keys, state = _np_out(T, np.int64), _np_out(8, np.int32)
+    check(lib.nerfhip_mesh_bvh_keys_host(vertices.ctypes.data, V, triangles.ctypes.data, T, keys.ctypes.data, state.ctypes.data),
+          "nerfhip_mesh_bvh_keys_host")
+    sorted_keys = _np16(np.sort(keys), np.int64)
+    tris, boxes = _np_out((T, 12), np.float32), _np_out((mesh_bvh_nodes(T), 6), np.float32)
+    check(lib.nerfhip_mesh_bvh_boxes_host(vertices.ctypes.data, V, triangles.ctypes.data, T, sorted_keys.ctypes.data, tris.ctypes.data,
+                                          boxes.ctypes.data), "nerfhip_mesh_bvh_boxes_host")
+    return tris, boxes, (sorted_keys & 0xffffffff).astype(np.int32), state[:1].copy()
+
+
+def _bvh_arg(what, tris, boxes):
+    tris = _require_dev(what, "tris", tris, torch.float32, (12,))
+    boxes = _require_dev(what, "boxes", boxes, torch.float32, (6,))
+    if boxes.shape[0] != mesh_bvh_nodes(tris.shape[0]):
+        raise ValueError("%s: a hierarchy of %d triangles has %d boxes, got %d" % (what, tris.shape[0], mesh_bvh_nodes(tris.shape[0]),
+                                                                                   boxes.shape[0]))
+    return tris, boxes
+
+
+@device_guard
+def mesh_cast(rays, tris, boxes):
+    """nerfhip_mesh_cast: rays (n, 8) fp32 against the hierarchy of `mesh_bvh_build` -> (tri (n,) int32: the original number of the
+    nearest triangle hit within [near, far], -1 for a miss; t (n,); b1 (n,); b2 (n,)), on the device."""
+    rays = _require_dev("mesh_cast", "rays", rays, torch.float32, (8,))
+    tris, boxes = _bvh_arg("mesh_cast", tris, boxes)
+    _same_device("mesh_cast", rays, tris, boxes)
+    n, dev = rays.shape[0], rays.device
+    tri = torch.empty(n, device=dev, dtype=torch.int32)
+    t, b1, b2 = (torch.empty(n, device=dev, dtype=torch.float32) for _ in range(3))
+    check(_lib.load().nerfhip_mesh_cast(ptr(rays), n, ptr(tris), ptr(boxes), tris.shape[0], ptr(tri), ptr(t), ptr(b1), ptr(b2),
+                                        stream_ptr()), "nerfhip_mesh_cast")
+    return tri, t, b1, b2
+
+
+def _rays_host(what, rays):
+    import numpy as np
+    rays = _np16(rays, np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("%s: rays must be (n, 8), got %s" % (what, rays.shape))
+    return rays
+
+
+def mesh_cast_host(rays, tris, boxes, brute=False):
+    """nerfhip_mesh_cast_host (host, no GPU): numpy rays (n, 8) against a numpy hierarchy -> numpy (tri, t, b1, b2), by the kernel's
+    own per-ray routine.  brute=True tests every triangle and reads no box (boxes may be None)."""
+    import numpy as np
+    rays = _rays_host("mesh_cast_host", rays)
+    tris = _np16(tris, np.float32)
+    if tris.ndim != 2 or tris.shape[1] != 12:
+        raise ValueError("mesh_cast_host: tris must be (T, 12), got %s" % (tris.shape,))
+    T = tris.shape[0]
+    if not brute:
+        boxes = _np16(boxes, np.float32)
+        if boxes.shape != (mesh_bvh_nodes(T), 6):
+            raise ValueError("mesh_cast_host: a hierarchy of %d triangles has %d boxes, got %s" % (T, mesh_bvh_nodes(T), boxes.shape))
+    n = rays.shape[0]
+    tri, t, b1, b2 = _np_out(n, np.int32), _np_out(n, np.float32), _np_out(n, np.float32), _np_out(n, np.float32)
+    check(_lib.load().nerfhip_mesh_cast_host(rays.ctypes.data, n, tris.ctypes.data, None if brute else boxes.ctypes.data, T,
+                                             int(bool(brute)), tri.ctypes.data, t.ctypes.data, b1.ctypes.data, b2.ctypes.data),
+          "nerfhip_mesh_cast_host")
+    return tri, t, b1, b2
+
+
+def _shade_scalars(what, ambient, background):
+    ambient, background = float(ambient), float(background)
+    if not 0.0 <= ambient <= 1.0:
+        raise ValueError("%s: ambient must be in [0, 1], got %r" % (what, ambient))
+    return ambient, background
+
+
+@device_guard
+def mesh_shade(rays, tri, b1, b2, vertices, triangles, colors=None, ambient=1.0, background=0.0):
+    """nerfhip_mesh_shade: the hits of `mesh_cast` -> rgb (n, 3): the barycentric blend of the vertex colours (colors (V, 3) uint8 /
+    255; None: white) times ambient + (1 - ambient) |n . d|, n the triangle's unit normal and d the unit direction; `background`
+    for a miss."""
+    rays = _require_dev("mesh_shade", "rays", rays, torch.float32, (8,))
+    tri = _require_dev("mesh_shade", "tri", tri, torch.int32, ())
+    b1 = _require_dev("mesh_shade", "b1", b1, torch.float32, ())
+    b2 = _require_dev("mesh_shade", "b2", b2, torch.float32, ())
+    vertices, triangles = _mesh_arrays("mesh_shade", vertices, triangles)
+    if colors is not None:
+        colors = _require_dev("mesh_shade", "colors", colors, torch.uint8, (3,))
+        if colors.shape[0] != vertices.shape[0]:
+            raise ValueError("mesh_shade: %d colours for %d vertices" % (colors.shape[0], vertices.shape[0]))
+    n = rays.shape[0]
+    if not tri.shape[0] == b1.shape[0] == b2.shape[0] == n:
+        raise ValueError("mesh_shade: tri, b1 and b2 must have one entry per ray")
+    _same_device("mesh_shade", rays, tri, b1, b2, vertices, triangles, colors)
+    ambient, background = _shade_scalars("mesh_shade", ambient, background)
+    rgb = torch.empty(n, 3, device=rays.device, dtype=torch.float32)
+    check(_lib.load().nerfhip_mesh_shade(ptr(rays), n, ptr(tri), ptr(b1), ptr(b2), ptr(vertices), vertices.shape[0], ptr(triangles),
+                                         triangles.shape[0], ptr(colors), ambient, background, ptr(rgb), stream_ptr()), "nerfhip_mesh_shade")
+    return rgb
+
+
+def mesh_shade_host(rays, tri, b1, b2, vertices, triangles, colors=None, ambient=1.0, background=0.0):
+    """nerfhip_mesh_shade_host (host, no GPU): numpy in, numpy rgb (n, 3) out."""
+    import numpy as np
+    rays = _rays_host("mesh_shade_host", rays)
+    tri, b1, b2 = _np16(tri, np.int32), _np16(b1, np.float32), _np16(b2, np.float32)
+    vertices, triangles = _mesh_arrays_host("mesh_shade_host", vertices, triangles)
+    n = rays.shape[0]
+    if not tri.shape == b1.shape == b2.shape == (n,):
+        raise ValueError("mesh_shade_host: tri, b1 and b2 must have one entry per ray")
+    if colors is not None:
+        colors = _np16(colors, np.uint8)
+        if colors.shape != vertices.shape:
+            raise ValueError("mesh_shade_host: colours must be (V, 3), got %s" % (colors.shape,))
+    ambient, background = _shade_scalars("mesh_shade_host", ambient, background)
+    rgb = _np_out((n, 3), np.float32)
+    check(_lib.load().nerfhip_mesh_shade_host(rays.ctypes.data, n, tri.ctypes.data, b1.ctypes.data, b2.ctypes.data, vertices.ctypes.data,
+                                              vertices.shape[0], triangles.ctypes.data, triangles.shape[0],
+                                              None if colors is None else colors.ctypes.data, ambient, background, rgb.ctypes.data),
+          "nerfhip_mesh_shade_host")
+    return rgb
+
+
+def _mixed_scalars(what, mode, tau, background):
+    if mode not in MIXED_MODES:
+        raise ValueError("%s: mode must be 'ztest' or 'clip', got %r" % (what, mode))
+    tau = float(tau)
+    if not tau > 0.0:
+        raise ValueError("%s: tau must be > 0, got %r" % (what, tau))
+    return MIXED_MODES[mode], tau, float(background)
+
+
+@device_guard
+def mixed_compose(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, background=0.0):
+    """nerfhip_mixed_compose: a render (rgb_n (n, 3), depth_n (n,), opacity_n (n,)) and a mesh layer (tri, t of `mesh_cast`, rgb_m of
+    `mesh_shade`) -> (rgb, depth, opacity, mask (n,) uint8).  'ztest': the mesh wins where it is hit and t < depth_n / opacity_n
+    (+inf where opacity_n < tau).  'clip': the render was made with far = min(far, t) on the hit rays and no background; the mesh,
+    or `background` on a miss, fills the transmittance it left (include/nerfhip.h)."""
+    code, tau, background = _mixed_scalars("mixed_compose", mode, tau, background)
+    rgb_n = _require_dev("mixed_compose", "rgb_n", rgb_n, torch.float32, (3,))
+    rgb_m = _require_dev("mixed_compose", "rgb_m", rgb_m, torch.float32, (3,))
+    depth_n = _require_dev("mixed_compose", "depth_n", depth_n, torch.float32, ())
+    opacity_n = _require_dev("mixed_compose", "opacity_n", opacity_n, torch.float32, ())
+    tri = _require_dev("mixed_compose", "tri", tri, torch.int32, ())
+    t = _require_dev("mixed_compose", "t", t, torch.float32, ())
+    n = rgb_n.shape[0]
+    if not rgb_m.shape[0] == depth_n.shape[0] == opacity_n.shape[0] == tri.shape[0] == t.shape[0] == n:
+        raise ValueError("mixed_compose: every input must have one row per ray")
+    _same_device("mixed_compose", rgb_n, depth_n, opacity_n, tri, t, rgb_m)
+    dev = rgb_n.device
+    rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
+    depth, opacity = torch.empty(n, device=dev, dtype=torch.float32), torch.empty(n, device=dev, dtype=torch.float32)
+    mask = torch.empty(n, device=dev, dtype=torch.uint8)
+    check(_lib.load().nerfhip_mixed_compose(code, n, ptr(rgb_n), ptr(depth_n), ptr(opacity_n), ptr(tri), ptr(t), ptr(rgb_m), tau, background,
+                                            ptr(rgb), ptr(depth), ptr(opacity), ptr(mask), stream_ptr()), "nerfhip_mixed_compose")
+    return rgb, depth, opacity, mask
+
+
+def mixed_compose_host(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, background=0.0):
+    """nerfhip_mixed_compose_host (host, no GPU): numpy in, numpy (rgb, depth, opacity, mask) out."""
+    import numpy as np
+    code, tau, background = _mixed_scalars("mixed_compose_host", mode, tau, background)
+    rgb_n, rgb_m = _np16(rgb_n, np.float32), _np16(rgb_m, np.float32)
+    depth_n, opacity_n, t, tri = _np16(depth_n, np.float32), _np16(opacity_n, np.float32), _np16(t, np.float32), _np16(tri, np.int32)
+    n = depth_n.shape[0]
+    if not (rgb_n.shape == rgb_m.shape == (n, 3) and depth_n.shape == opacity_n.shape == t.shape == tri.shape == (n,)):
+        raise ValueError("mixed_compose_host: every input must have one row per ray")
+    rgb, depth, opacity, mask = _np_out((n, 3), np.float32), _np_out(n, np.float32), _np_out(n, np.float32), _np_out(n, np.uint8)
+    check(_lib.load().nerfhip_mixed_compose_host(code, n, rgb_n.ctypes.data, depth_n.ctypes.data, opacity_n.ctypes.data, tri.ctypes.data,
+                                                 t.ctypes.data, rgb_m.ctypes.data, tau, background, rgb.ctypes.data, depth.ctypes.data,
+                                                 opacity.ctypes.data, mask.ctypes.data), "nerfhip_mixed_compose_host")
+    return rgb, depth, opacity, mask
