@@ -9,19 +9,22 @@
 // Nothing allocates, nothing synchronises; no texture objects, no LDS, no scratch.
 #include "common.h"
 #include "baked_core.h"
+#include "twin_launch.h"
 
 namespace {
 
 using nerfhip::BakedPixel;
 using nerfhip::BakedVol;
 using nerfhip::baked_point_index;
+using nerfhip::blocks_of;
+using nerfhip::finite_f32;
+using nerfhip::kMaxRays;
+using nerfhip::misaligned;
 
-constexpr int kBlock = 256;
+constexpr int kBlock = nerfhip::kItemBlock;
 constexpr int kWave = 64;
 constexpr int kMaxN = 1625;                    // N^3 < 2^32: the file's point index is a uint32
-constexpr int64_t kMaxRays = (int64_t)1 << 30;
 
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 inline bool lattice_ok(int N) { return N >= 2 && N <= kMaxN; }
 inline int64_t point_bricks(int N) { return (N + 7) / 8; }
 inline int64_t cell_bricks(int N) { return (N - 1 + 7) / 8; }
@@ -83,37 +86,45 @@ __global__ void __launch_bounds__(kWave) baked_bricks(const uint32_t* __restrict
 }
 
 // ---- render -------------------------------------------------------------------------------------------------------------------
+struct RenderItem {
+    const float4* rays;
+    BakedVol v;
+    float *rgb, *depth, *opacity;    // each may be null
+    __host__ __device__ void operator()(int64_t i) const {
+        float ray[8];
+        nerfhip::load_ray(rays, i, ray);
+        const BakedPixel px = nerfhip::baked_march(v, ray);
+        if (rgb) {
+            rgb[3 * i] = px.rgb[0];
+            rgb[3 * i + 1] = px.rgb[1];
+            rgb[3 * i + 2] = px.rgb[2];
+        }
+        if (depth) depth[i] = px.depth;
+        if (opacity) opacity[i] = px.opacity;
+    }
+};
+
 __global__ void __launch_bounds__(kBlock) baked_render(const float4* __restrict__ rays, int64_t n, BakedVol v, float* __restrict__ rgb,
                                                        float* __restrict__ depth, float* __restrict__ opacity) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 a = rays[2 * i], b = rays[2 * i + 1];
-    const float ray[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const BakedPixel px = nerfhip::baked_march(v, ray);
-    if (rgb) {
-        rgb[3 * i] = px.rgb[0];
-        rgb[3 * i + 1] = px.rgb[1];
-        rgb[3 * i + 2] = px.rgb[2];
-    }
-    if (depth) depth[i] = px.depth;
-    if (opacity) opacity[i] = px.opacity;
+    const int64_t i = nerfhip::item_index();
+    if (i < n) RenderItem{rays, v, rgb, depth, opacity}(i);
 }
 
 // The checks of the two render entry points: everything that can be refused is refused before a pointer is touched.
 inline int render_args(const float* rays, int64_t n, const uint8_t* data, const int32_t* words, int N, const float* ranges, float cell,
                        float step, float t_stop, int white_back, const float* rgb, const float* depth, const float* opacity, BakedVol& v) {
     NERFHIP_CHECK_ARG(n >= 0 && n <= kMaxRays && lattice_ok(N) && ranges);
-    NERFHIP_CHECK_ARG(cell > 0.0f && nerfhip::baked_finite(cell));
+    NERFHIP_CHECK_ARG(cell > 0.0f && finite_f32(cell));
     NERFHIP_CHECK_ARG(step >= 0.0625f && step <= 8.0f);
     NERFHIP_CHECK_ARG(t_stop >= 0.0f && t_stop < 1.0f);
     double diag2 = 0.0;
     for (int a = 0; a < 3; ++a) {
         const float lo = ranges[2 * a], hi = ranges[2 * a + 1];
-        NERFHIP_CHECK_ARG(nerfhip::baked_finite(lo) && nerfhip::baked_finite(hi) && lo < hi);
+        NERFHIP_CHECK_ARG(finite_f32(lo) && finite_f32(hi) && lo < hi);
         v.lo[a] = lo;
         v.hi[a] = hi;
         v.scale[a] = (float)(N - 1) / (hi - lo);
-        NERFHIP_CHECK_ARG(v.scale[a] > 0.0f && nerfhip::baked_finite(v.scale[a]));
+        NERFHIP_CHECK_ARG(v.scale[a] > 0.0f && finite_f32(v.scale[a]));
         diag2 += ((double)hi - (double)lo) * ((double)hi - (double)lo);
     }
     // the longest chord must not need more segments than a march may take
@@ -129,8 +140,8 @@ inline int render_args(const float* rays, int64_t n, const uint8_t* data, const 
     v.white_back = white_back ? 1 : 0;
     if (n == 0) return 0;
     NERFHIP_CHECK_ARG(rays && data);
-    if ((((uintptr_t)rays) & 15) || (((uintptr_t)data) & 15) ||
-        ((((uintptr_t)words) | ((uintptr_t)rgb) | ((uintptr_t)depth) | ((uintptr_t)opacity)) & 3))
+    if (misaligned(rays, 16) || misaligned(data, 16) || misaligned(words, 4) || misaligned(rgb, 4) || misaligned(depth, 4) ||
+        misaligned(opacity, 4))
         return NERFHIP_E_ALIGN;
     return 0;
 }
@@ -145,7 +156,7 @@ extern "C" size_t nerfhip_baked_bytes(int N) {
 
 extern "C" int nerfhip_baked_scatter(const int32_t* records, int64_t K, int N, uint8_t* data, int32_t* n_bad, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(lattice_ok(N) && K >= 0 && K <= ((int64_t)1 << 32) && data && n_bad && (records || K == 0));
-    if ((((uintptr_t)data) & 15) || (((uintptr_t)records) & 7) || (((uintptr_t)n_bad) & 3)) return NERFHIP_E_ALIGN;
+    if (misaligned(data, 16) || misaligned(records, 8) || misaligned(n_bad, 4)) return NERFHIP_E_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n16 = bricked_points(N) / 4;
     hipLaunchKernelGGL(baked_clear, dim3(blocks_of(n16)), dim3(kBlock), 0, s, (uint4*)data, n16, n_bad);
@@ -157,7 +168,7 @@ extern "C" int nerfhip_baked_scatter(const int32_t* records, int64_t K, int N, u
 
 extern "C" int nerfhip_baked_from_dense(const uint8_t* rgba, int N, uint8_t* data, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(lattice_ok(N) && rgba && data);
-    if ((((uintptr_t)data) & 15) || (((uintptr_t)rgba) & 3)) return NERFHIP_E_ALIGN;
+    if (misaligned(data, 16) || misaligned(rgba, 4)) return NERFHIP_E_ALIGN;
     const int64_t n_points = bricked_points(N);
     hipLaunchKernelGGL(baked_permute, dim3(blocks_of(n_points)), dim3(kBlock), 0, (hipStream_t)stream, (const uint32_t*)rgba, (uint32_t)N,
                        (uint32_t)point_bricks(N), n_points, (uint32_t*)data);
@@ -166,7 +177,7 @@ extern "C" int nerfhip_baked_from_dense(const uint8_t* rgba, int N, uint8_t* dat
 
 extern "C" int nerfhip_baked_bricks(const uint8_t* data, int N, int32_t* words, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(lattice_ok(N) && data && words);
-    if ((((uintptr_t)data) & 15) || (((uintptr_t)words) & 3)) return NERFHIP_E_ALIGN;
+    if (misaligned(data, 16) || misaligned(words, 4)) return NERFHIP_E_ALIGN;
     const int64_t MB = cell_bricks(N);
     const uint32_t n_bricks = (uint32_t)(MB * MB * MB), n_words = (n_bricks + 31) / 32;
     hipLaunchKernelGGL(baked_bricks, dim3(n_words), dim3(kWave), 0, (hipStream_t)stream, (const uint32_t*)data, N, (int)point_bricks(N),
@@ -191,15 +202,6 @@ extern "C" int nerfhip_baked_render_host(const float* rays, int64_t n, const uin
     BakedVol v;
     const int e = render_args(rays, n, data, words_or_null, N, ranges_host, cell, step, t_stop, white_back, rgb, depth, opacity, v);
     if (e || n == 0) return e;
-    for (int64_t i = 0; i < n; ++i) {
-        const BakedPixel px = nerfhip::baked_march(v, rays + 8 * i);
-        if (rgb) {
-            rgb[3 * i] = px.rgb[0];
-            rgb[3 * i + 1] = px.rgb[1];
-            rgb[3 * i + 2] = px.rgb[2];
-        }
-        if (depth) depth[i] = px.depth;
-        if (opacity) opacity[i] = px.opacity;
-    }
+    nerfhip::host_items(n, RenderItem{(const float4*)rays, v, rgb, depth, opacity});
     return 0;
 }

@@ -15,14 +15,7 @@
 // keeps that margin far above the fp32 error of a lattice coordinate.  The landing sample tests its own bit like any other, and a
 // landing outside the brick the leap started in takes the leap back: no sample is skipped on the strength of the walk alone.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define NH_BAKED_HD __host__ __device__ inline
-#else
-#define NH_BAKED_HD inline
-#endif
+#include "twin.h"
 
 namespace nerfhip {
 
@@ -42,52 +35,34 @@ struct BakedPixel {
     float rgb[3], depth, opacity;
 };
 
-NH_BAKED_HD bool baked_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }    // false for NaN and +-inf
-
 // The position, in points, of lattice point (iy, ix, iz) in the bricked volume.
-NH_BAKED_HD uint64_t baked_point_index(int NB, uint32_t iy, uint32_t ix, uint32_t iz) {
+NH_TWIN_HD uint64_t baked_point_index(int NB, uint32_t iy, uint32_t ix, uint32_t iz) {
     const uint64_t brick = ((uint64_t)(iy >> 3) * (uint32_t)NB + (ix >> 3)) * (uint32_t)NB + (iz >> 3);
     const uint32_t local = ((((iy & 7u) << 3) | (ix & 7u)) << 3) | (iz & 7u);
     return (brick << 9) | local;
 }
 
-NH_BAKED_HD BakedPixel baked_march(const BakedVol& v, const float* __restrict__ ray) {
+NH_TWIN_HD BakedPixel baked_march(const BakedVol& v, const float* __restrict__ ray) {
     const float bg = v.white_back ? 1.0f : 0.0f;
     BakedPixel px;
     px.rgb[0] = px.rgb[1] = px.rgb[2] = bg;
     px.depth = 0.0f;
     px.opacity = 0.0f;
 
-    float o[3], d[3];
-    const float near = ray[6], far = ray[7];
-    bool finite = baked_finite(near) && baked_finite(far);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        o[a] = ray[a];
-        d[a] = ray[3 + a];
-        finite = finite && baked_finite(o[a]) && baked_finite(d[a]);
-    }
-    if (!finite) return px;
+    const RayRow row = ray_row(ray);
+    if (!row.finite) return px;
+    const float* o = row.o;
+    const float* d = row.d;
     const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (!(dn > 0.0f) || !baked_finite(dn)) return px;    // a zero direction (also one whose squares underflow or overflow)
-
-    // clip [near, far] to the box; a zero component (either sign) leaves the interval alone or misses, and never divides
-    float t_in = near, t_out = far;
-    float rd[3], h[3];
+    if (!(dn > 0.0f) || !finite_f32(dn)) return px;      // a zero direction (also one whose squares underflow or overflow)
+    float t_in, t_out;
+    if (!ray_clip_box(row, v.lo, v.hi, t_in, t_out)) return px;
+    float rd[3], h[3];                                   // what a leap needs: 1 / d (0 for a zero component) and the point spacing
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         h[a] = (v.hi[a] - v.lo[a]) / (float)(v.N - 1);
-        rd[a] = 0.0f;
-        if (d[a] == 0.0f) {
-            if (o[a] < v.lo[a] || o[a] > v.hi[a]) return px;
-            continue;
-        }
-        rd[a] = 1.0f / d[a];
-        const float ta = (v.lo[a] - o[a]) / d[a], tb = (v.hi[a] - o[a]) / d[a];
-        t_in = fmaxf(t_in, fminf(ta, tb));
-        t_out = fminf(t_out, fmaxf(ta, tb));
+        rd[a] = d[a] == 0.0f ? 0.0f : 1.0f / d[a];
     }
-    if (!(t_in < t_out)) return px;
 
     const float dt = (v.step * v.cell) / dn;
     if (!(dt > 0.0f)) return px;

@@ -9,15 +9,15 @@
 //                  epochs on replay.
 #include "epoch_core.h"
 #include "rays_math.h"
+#include "twin_launch.h"
 
 namespace {
 
+using nerfhip::blocks_of;
 using nerfhip::EpochKey;
 
-constexpr int kBlock = 256;
+constexpr int kBlock = nerfhip::kItemBlock;
 constexpr int64_t kMaxBatch = (int64_t)1 << 30;
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 __global__ void __launch_bounds__(kBlock) epoch_ids_kernel(EpochKey key, int64_t n, int rank, int world, int64_t first, int64_t count,
                                                            int64_t* __restrict__ out) {

@@ -20,13 +20,7 @@
 // so a step lands in [0, n) with probability above 1/2 and the expected number of encryptions is below 2.  Restricting a
 // permutation to the first return into a subset is again a permutation: epoch_perm(key, n, .) is a bijection on [0, n).
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define NH_EPOCH_HD __host__ __device__ inline
-#else
-#define NH_EPOCH_HD inline
-#endif
+#include "twin.h"
 
 namespace nerfhip {
 
@@ -37,7 +31,7 @@ struct EpochKey {
     uint32_t rk[kEpochRounds];
 };
 
-NH_EPOCH_HD uint64_t epoch_splitmix64(uint64_t& s) {
+NH_TWIN_HD uint64_t epoch_splitmix64(uint64_t& s) {
     s += 0x9E3779B97F4A7C15ull;
     uint64_t z = s;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -45,7 +39,7 @@ NH_EPOCH_HD uint64_t epoch_splitmix64(uint64_t& s) {
     return z ^ (z >> 31);
 }
 
-NH_EPOCH_HD EpochKey epoch_key(uint64_t seed, uint64_t epoch) {
+NH_TWIN_HD EpochKey epoch_key(uint64_t seed, uint64_t epoch) {
     uint64_t s = seed;
     s = epoch_splitmix64(s) ^ epoch;
     EpochKey k;
@@ -54,7 +48,7 @@ NH_EPOCH_HD EpochKey epoch_key(uint64_t seed, uint64_t epoch) {
     return k;
 }
 
-NH_EPOCH_HD uint32_t epoch_fmix32(uint32_t h) {
+NH_TWIN_HD uint32_t epoch_fmix32(uint32_t h) {
     h ^= h >> 16;
     h *= 0x85EBCA6Bu;
     h ^= h >> 13;
@@ -64,14 +58,14 @@ NH_EPOCH_HD uint32_t epoch_fmix32(uint32_t h) {
 }
 
 // max(2, ceil(log2 n)) for 2 <= n <= 2^40
-NH_EPOCH_HD int epoch_bits(uint64_t n) {
+NH_TWIN_HD int epoch_bits(uint64_t n) {
     int b = 2;
     while (b < 40 && ((uint64_t)1 << b) < n) ++b;
     return b;
 }
 
 // one encryption of the b-bit value v (both halves are at most 20 bits wide)
-NH_EPOCH_HD uint64_t epoch_encrypt(const EpochKey& k, int b, uint64_t v) {
+NH_TWIN_HD uint64_t epoch_encrypt(const EpochKey& k, int b, uint64_t v) {
     int wr = b >> 1, wl = b - wr;
     uint32_t L = (uint32_t)(v >> wr), R = (uint32_t)v & ((1u << wr) - 1u);
 #pragma unroll
@@ -88,7 +82,7 @@ NH_EPOCH_HD uint64_t epoch_encrypt(const EpochKey& k, int b, uint64_t v) {
 }
 
 // position p in [0, n) -> id in [0, n);  1 <= n <= 2^40
-NH_EPOCH_HD uint64_t epoch_perm(const EpochKey& k, uint64_t n, uint64_t p) {
+NH_TWIN_HD uint64_t epoch_perm(const EpochKey& k, uint64_t n, uint64_t p) {
     if (n == 1) return 0;
     const int b = epoch_bits(n);
     const uint64_t limit = ((uint64_t)1 << b) - n + 1;
@@ -102,8 +96,8 @@ NH_EPOCH_HD uint64_t epoch_perm(const EpochKey& k, uint64_t n, uint64_t p) {
 
 // Ranks (torch's DistributedSampler): rank r of `world` owns ceil(n / world) positions, its j-th one is (j world + r) mod n — the
 // wrap is the sampler's padding.
-NH_EPOCH_HD int64_t epoch_rank_share(int64_t n, int world) { return (n + world - 1) / world; }
-NH_EPOCH_HD uint64_t epoch_rank_id(const EpochKey& k, int64_t n, int rank, int world, int64_t j) {
+NH_TWIN_HD int64_t epoch_rank_share(int64_t n, int world) { return (n + world - 1) / world; }
+NH_TWIN_HD uint64_t epoch_rank_id(const EpochKey& k, int64_t n, int rank, int world, int64_t j) {
     return epoch_perm(k, (uint64_t)n, (uint64_t)((j * world + rank) % n));
 }
 

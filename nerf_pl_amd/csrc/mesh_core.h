@@ -13,14 +13,7 @@
 // point-in-triangle test of the *sheared fp32 vertices*, and two triangles sharing an edge evaluate that edge's function from the
 // same two sheared vertices with opposite sign: no ray passes between them.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define NH_MESH_HD __host__ __device__ inline
-#else
-#define NH_MESH_HD inline
-#endif
+#include "twin.h"
 
 namespace nerfhip {
 
@@ -49,38 +42,18 @@ struct MeshHit {
     float t, b1, b2;
 };
 
-NH_MESH_HD bool mesh_finite(float v) {
-    const float a = v < 0.0f ? -v : v;
-    return a <= 3.402823466e+38f;    // false for NaN and +-inf
-}
-NH_MESH_HD float mesh_abs(float v) { return v < 0.0f ? -v : v; }
-NH_MESH_HD uint32_t mesh_bits(float v) {
-    union {
-        float f;
-        uint32_t u;
-    } c;
-    c.f = v;
-    return c.u;
-}
-NH_MESH_HD float mesh_from_bits(uint32_t u) {
-    union {
-        float f;
-        uint32_t u;
-    } c;
-    c.u = u;
-    return c.f;
-}
+NH_TWIN_HD float mesh_abs(float v) { return v < 0.0f ? -v : v; }
 // min and max in the total order that puts -0 below +0: exact and independent of the order of the operands (no NaN reaches them)
-NH_MESH_HD float mesh_min(float a, float b) { return (b < a || (b == a && (mesh_bits(b) >> 31))) ? b : a; }
-NH_MESH_HD float mesh_max(float a, float b) { return (b > a || (b == a && !(mesh_bits(b) >> 31))) ? b : a; }
+NH_TWIN_HD float mesh_min(float a, float b) { return (b < a || (b == a && (float_bits(b) >> 31))) ? b : a; }
+NH_TWIN_HD float mesh_max(float a, float b) { return (b > a || (b == a && !(float_bits(b) >> 31))) ? b : a; }
 // the same order on unsigned integers, for the atomics of the bounds
-NH_MESH_HD uint32_t mesh_ordered(float v) {
-    const uint32_t u = mesh_bits(v);
+NH_TWIN_HD uint32_t mesh_ordered(float v) {
+    const uint32_t u = float_bits(v);
     return (u >> 31) ? ~u : (u | 0x80000000u);
 }
-NH_MESH_HD float mesh_unordered(uint32_t e) { return mesh_from_bits((e >> 31) ? (e & 0x7fffffffu) : ~e); }
+NH_TWIN_HD float mesh_unordered(uint32_t e) { return float_from_bits((e >> 31) ? (e & 0x7fffffffu) : ~e); }
 
-NH_MESH_HD int mesh_levels(int64_t T) {
+NH_TWIN_HD int mesh_levels(int64_t T) {
     if (T <= 0) return 0;
     int64_t n = (T + kMeshLeaf - 1) / kMeshLeaf;
     int levels = 1;
@@ -90,7 +63,7 @@ NH_MESH_HD int mesh_levels(int64_t T) {
     }
     return levels;
 }
-NH_MESH_HD int64_t mesh_nodes(int64_t T) {
+NH_TWIN_HD int64_t mesh_nodes(int64_t T) {
     if (T <= 0) return 0;
     int64_t n = (T + kMeshLeaf - 1) / kMeshLeaf, total = n;
     while (n > 1) {
@@ -100,11 +73,11 @@ NH_MESH_HD int64_t mesh_nodes(int64_t T) {
     return total;
 }
 // nodes of level k: ceil(n0 / 8^k)  (a ceiling of ceilings is the ceiling of the whole)
-NH_MESH_HD int mesh_level_nodes(int n0, int k) { return (int)(((int64_t)n0 + (((int64_t)1 << (3 * k)) - 1)) >> (3 * k)); }
+NH_TWIN_HD int mesh_level_nodes(int n0, int k) { return (int)(((int64_t)n0 + (((int64_t)1 << (3 * k)) - 1)) >> (3 * k)); }
 
 // ---- build --------------------------------------------------------------------------------------------------------------------
 // The 9 coordinates of triangle t, or false for a bad triangle: an index outside [0, V) or a non-finite coordinate.
-NH_MESH_HD bool mesh_triangle(const float* __restrict__ vertices, int64_t V, const int32_t* __restrict__ triangles, int64_t t,
+NH_TWIN_HD bool mesh_triangle(const float* __restrict__ vertices, int64_t V, const int32_t* __restrict__ triangles, int64_t t,
                               float* __restrict__ p) {
     bool ok = true;
 #pragma unroll
@@ -116,13 +89,13 @@ NH_MESH_HD bool mesh_triangle(const float* __restrict__ vertices, int64_t V, con
         for (int a = 0; a < 3; ++a) {
             const float x = in ? vertices[3 * (int64_t)v + a] : 0.0f;
             p[3 * c + a] = x;
-            ok = ok && mesh_finite(x);
+            ok = ok && finite_f32(x);
         }
     }
     return ok;
 }
 
-NH_MESH_HD uint32_t mesh_spread10(uint32_t v) {    // 10 bits -> every third bit
+NH_TWIN_HD uint32_t mesh_spread10(uint32_t v) {    // 10 bits -> every third bit
     v = (v | (v << 16)) & 0x030000ffu;
     v = (v | (v << 8)) & 0x0300f00fu;
     v = (v | (v << 4)) & 0x030c30c3u;
@@ -131,7 +104,7 @@ NH_MESH_HD uint32_t mesh_spread10(uint32_t v) {    // 10 bits -> every third bit
 }
 
 // morton30 of the centroid quantised to 10 bits per axis in [lo, hi] (x in the highest bit of every triple) << 32 | t.
-NH_MESH_HD int64_t mesh_key(const float* __restrict__ p, bool ok, const float* __restrict__ lo, const float* __restrict__ hi, int64_t t) {
+NH_TWIN_HD int64_t mesh_key(const float* __restrict__ p, bool ok, const float* __restrict__ lo, const float* __restrict__ hi, int64_t t) {
     uint32_t m = kMeshBadMorton;
     if (ok) {
         uint32_t q[3];
@@ -150,9 +123,9 @@ NH_MESH_HD int64_t mesh_key(const float* __restrict__ p, bool ok, const float* _
 // Leaf j: packs its (up to) 4 sorted triangles and writes their box.  A bad triangle, or a key whose index is outside [0, T),
 // is stored with index -1 and zero coordinates and adds nothing to the box; a leaf of bad triangles only has the empty box
 // (lo = +inf, hi = -inf), the neutral element of the levels above.
-NH_MESH_HD void mesh_leaf(const float* __restrict__ vertices, int64_t V, const int32_t* __restrict__ triangles, int64_t T,
+NH_TWIN_HD void mesh_leaf(const float* __restrict__ vertices, int64_t V, const int32_t* __restrict__ triangles, int64_t T,
                           const int64_t* __restrict__ sorted_keys, int64_t j, MeshVec4* __restrict__ tris, float* __restrict__ boxes) {
-    const float inf = mesh_from_bits(0x7f800000u);
+    const float inf = float_from_bits(0x7f800000u);
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
     for (int64_t s = kMeshLeaf * j; s < kMeshLeaf * j + kMeshLeaf && s < T; ++s) {
         const int64_t t = (int64_t)(uint32_t)((uint64_t)sorted_keys[s] & 0xffffffffu);
@@ -166,7 +139,7 @@ NH_MESH_HD void mesh_leaf(const float* __restrict__ vertices, int64_t V, const i
             u[c].z = ok ? p[3 * c + 2] : 0.0f;
             u[c].w = 0.0f;
         }
-        u[0].w = mesh_from_bits(ok ? (uint32_t)t : 0xffffffffu);
+        u[0].w = float_from_bits(ok ? (uint32_t)t : 0xffffffffu);
 #pragma unroll
         for (int c = 0; c < 3; ++c) tris[3 * s + c] = u[c];
         if (ok) {
@@ -187,8 +160,8 @@ NH_MESH_HD void mesh_leaf(const float* __restrict__ vertices, int64_t V, const i
 }
 
 // Node i of a level above the leaves: the union of children [8 i, 8 i + 8) ∩ [0, n_child) of the level below.
-NH_MESH_HD void mesh_node(const float* __restrict__ child, int n_child, int i, float* __restrict__ out) {
-    const float inf = mesh_from_bits(0x7f800000u);
+NH_TWIN_HD void mesh_node(const float* __restrict__ child, int n_child, int i, float* __restrict__ out) {
+    const float inf = float_from_bits(0x7f800000u);
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
     for (int c = kMeshFan * i; c < kMeshFan * i + kMeshFan && c < n_child; ++c) {
 #pragma unroll
@@ -205,34 +178,24 @@ NH_MESH_HD void mesh_node(const float* __restrict__ child, int n_child, int i, f
 }
 
 // ---- cast ---------------------------------------------------------------------------------------------------------------------
-NH_MESH_HD float mesh_pick(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
+NH_TWIN_HD float mesh_pick(float x, float y, float z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
 
-// What the ray contributes to every triangle test.
-struct MeshRay {
-    float o[3], d[3];
-    float near, far;
+// What the ray contributes to every triangle test: its row, and the shear of the watertight test.
+struct MeshRay : RayRow {
     int kx, ky, kz;
     float Sx, Sy, Sz;
     bool valid;
 };
 
 // valid = false: the ray hits nothing (a non-finite value in any column, or a zero direction).  Every field is set on every path.
-NH_MESH_HD MeshRay mesh_ray(const float* __restrict__ ray) {
+NH_TWIN_HD MeshRay mesh_ray(const float* __restrict__ ray) {
     MeshRay r;
-    bool finite = mesh_finite(ray[6]) && mesh_finite(ray[7]);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        r.o[a] = ray[a];
-        r.d[a] = ray[3 + a];
-        finite = finite && mesh_finite(r.o[a]) && mesh_finite(r.d[a]);
-    }
-    r.near = ray[6];
-    r.far = ray[7];
+    static_cast<RayRow&>(r) = ray_row(ray);
     const float ax = mesh_abs(r.d[0]), ay = mesh_abs(r.d[1]), az = mesh_abs(r.d[2]);
     const int kz = ax >= ay ? (ax >= az ? 0 : 2) : (ay >= az ? 1 : 2);
     const int k1 = kz == 2 ? 0 : kz + 1, k2 = k1 == 2 ? 0 : k1 + 1;
     const float dk = mesh_pick(r.d[0], r.d[1], r.d[2], kz);
-    r.valid = finite && dk != 0.0f;
+    r.valid = r.finite && dk != 0.0f;
     const float dz = r.valid ? dk : 1.0f;
     r.kz = kz;
     r.kx = dz < 0.0f ? k2 : k1;    // swapped for a negative dominant component: keeps the winding
@@ -245,8 +208,8 @@ NH_MESH_HD MeshRay mesh_ray(const float* __restrict__ ray) {
 
 // One triangle against the ray: updates `best` when it is hit within [near, far] and nearer than `best`, or as near with a lower
 // index.  Two-sided.  `best.tri` < 0 means nothing was hit so far.
-NH_MESH_HD void mesh_test(const MeshRay& r, const MeshVec4& v0, const MeshVec4& v1, const MeshVec4& v2, MeshHit& best) {
-    const int32_t index = (int32_t)mesh_bits(v0.w);
+NH_TWIN_HD void mesh_test(const MeshRay& r, const MeshVec4& v0, const MeshVec4& v1, const MeshVec4& v2, MeshHit& best) {
+    const int32_t index = (int32_t)float_bits(v0.w);
     if (index < 0) return;    // a bad triangle
     const float a0 = v0.x - r.o[0], a1 = v0.y - r.o[1], a2 = v0.z - r.o[2];
     const float b0 = v1.x - r.o[0], b1 = v1.y - r.o[1], b2 = v1.z - r.o[2];
@@ -289,7 +252,7 @@ NH_MESH_HD void mesh_test(const MeshRay& r, const MeshVec4& v0, const MeshVec4& 
 // divides: the axis only asks whether the origin lies within the widened slab.  The interval is cut to [near, limit] with
 // limit = min(far, best t so far), keeping t == limit because an equal t with a lower index still wins.  A non-finite M (a box
 // 1e38 wide) prunes nothing.  The empty box (lo > hi) holds nothing.
-NH_MESH_HD bool mesh_box_may_hit(const MeshRay& r, const float* __restrict__ box, float limit) {
+NH_TWIN_HD bool mesh_box_may_hit(const MeshRay& r, const float* __restrict__ box, float limit) {
     if (box[0] > box[3]) return false;
     float el[3], eh[3], M = 0.0f;
 #pragma unroll
@@ -300,7 +263,7 @@ NH_MESH_HD bool mesh_box_may_hit(const MeshRay& r, const float* __restrict__ box
         M = m0 > M ? m0 : M;
         M = m1 > M ? m1 : M;
     }
-    if (!mesh_finite(M)) return true;
+    if (!finite_f32(M)) return true;
     const float delta = M * 3.814697265625e-06f + 1.17549435e-38f;    // 2^-18 M + the smallest normal number
     float tn = r.near, tf = limit;
 #pragma unroll
@@ -326,7 +289,7 @@ NH_MESH_HD bool mesh_box_may_hit(const MeshRay& r, const float* __restrict__ box
 // so the loop body runs at most n_nodes times — the hard bound of the loop counter below, for any input, boxes of garbage
 // included — and the inner climb at most `levels` <= 10 times.  The level's size and offset come from n0 by arithmetic
 // (mesh_level_nodes), so no private array is indexed and nothing lands in scratch.
-NH_MESH_HD MeshHit mesh_cast_ray(const MeshBvh& b, const float* __restrict__ ray) {
+NH_TWIN_HD MeshHit mesh_cast_ray(const MeshBvh& b, const float* __restrict__ ray) {
     MeshHit best;
     best.tri = -1;
     best.t = best.b1 = best.b2 = 0.0f;
@@ -384,7 +347,7 @@ NH_MESH_HD MeshHit mesh_cast_ray(const MeshBvh& b, const float* __restrict__ ray
 // ambient + (1 - ambient) |n . d| / (|n| |d|), n the geometric normal; the background for a miss, for a triangle index outside
 // [0, T) and for a triangle that names a vertex outside [0, V).  A normal or direction of zero or non-finite length shades with
 // `ambient` alone.
-NH_MESH_HD void mesh_shade_ray(const float* __restrict__ ray, int32_t tri, float b1, float b2, const float* __restrict__ vertices,
+NH_TWIN_HD void mesh_shade_ray(const float* __restrict__ ray, int32_t tri, float b1, float b2, const float* __restrict__ vertices,
                                int64_t V, const int32_t* __restrict__ triangles, int64_t T, const uint8_t* __restrict__ colors,
                                float ambient, float background, float* __restrict__ rgb) {
     rgb[0] = rgb[1] = rgb[2] = background;
@@ -404,7 +367,7 @@ NH_MESH_HD void mesh_shade_ray(const float* __restrict__ ray, int32_t tri, float
     const float nd = (n[0] * d[0] + n[1] * d[1]) + n[2] * d[2];
     const float len = sqrtf(nn) * sqrtf(dd);
     float cosine = 0.0f;
-    if (len > 0.0f && mesh_finite(len) && mesh_finite(nd)) {
+    if (len > 0.0f && finite_f32(len) && finite_f32(nd)) {
         cosine = mesh_abs(nd) / len;
         cosine = cosine > 1.0f ? 1.0f : cosine;
     }
@@ -433,12 +396,12 @@ struct MixedPixel {
 // clip: the inner render was made with far = min(far, t) on hit rays and without a background; the mesh (or the background on a
 // miss) fills what it left: rgb = rgb_n + (1 - opacity_n) (hit ? rgb_m : background), depth = depth_n + (1 - opacity_n) t and
 // opacity = 1 on a hit, depth_n and opacity_n on a miss; mask = hit.
-NH_MESH_HD MixedPixel mixed_compose_ray(int mode, const float* __restrict__ rgb_n, float depth_n, float opacity_n, int32_t tri, float t,
+NH_TWIN_HD MixedPixel mixed_compose_ray(int mode, const float* __restrict__ rgb_n, float depth_n, float opacity_n, int32_t tri, float t,
                                         const float* __restrict__ rgb_m, float tau, float background) {
     MixedPixel px;
     const bool hit = tri >= 0;
     if (mode == kMixedZtest) {
-        const float s = opacity_n >= tau ? depth_n / opacity_n : mesh_from_bits(0x7f800000u);
+        const float s = opacity_n >= tau ? depth_n / opacity_n : float_from_bits(0x7f800000u);
         const bool mesh = hit && t < s;
         for (int a = 0; a < 3; ++a) px.rgb[a] = mesh ? rgb_m[a] : rgb_n[a];
         px.depth = mesh ? t : depth_n;

@@ -12,32 +12,32 @@
 // Nothing allocates, nothing synchronises; no LDS, no scratch.
 #include "common.h"
 #include "mesh_core.h"
+#include "twin_launch.h"
 
 namespace {
 
+using nerfhip::blocks_of;
+using nerfhip::kMaxRays;
 using nerfhip::MeshBvh;
 using nerfhip::MeshHit;
 using nerfhip::MeshVec4;
+using nerfhip::misaligned;
 using nerfhip::MixedPixel;
 
-constexpr int kBlock = 256;
-constexpr int64_t kMaxRays = (int64_t)1 << 30;
+constexpr int kBlock = nerfhip::kItemBlock;
 constexpr int64_t kMaxVertices = 0x7fffffff;    // a triangle names its vertices by int32
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-inline bool misaligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) != 0; }
 
 // ---- build --------------------------------------------------------------------------------------------------------------------
 // state: 8 words.  [0] the number of bad triangles, [1] zero, [2..4] / [5..7] the bounds' lo / hi in mesh_ordered's encoding.
 __global__ void mesh_state_init(uint32_t* __restrict__ state) {
     const int i = threadIdx.x;
-    if (i < 8) state[i] = i < 2 ? 0u : nerfhip::mesh_ordered(nerfhip::mesh_from_bits(i < 5 ? 0x7f800000u : 0xff800000u));
+    if (i < 8) state[i] = i < 2 ? 0u : nerfhip::mesh_ordered(nerfhip::float_from_bits(i < 5 ? 0x7f800000u : 0xff800000u));
 }
 
 __global__ void __launch_bounds__(kBlock) mesh_bounds(const float* __restrict__ vertices, int64_t V, const int32_t* __restrict__ triangles,
                                                       int64_t T, uint32_t* __restrict__ state) {
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const float inf = nerfhip::mesh_from_bits(0x7f800000u);
+    const float inf = nerfhip::float_from_bits(0x7f800000u);
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
     int bad = 0;
     if (t < T) {
@@ -122,47 +122,82 @@ inline MeshBvh bvh_of(const float* tris, const float* boxes, int64_t T) {
 }
 
 // ---- cast, shade, compose -----------------------------------------------------------------------------------------------------
+struct CastItem {
+    const float4* rays;
+    const MeshBvh& b;    // by reference: held by value, hipcc orders the traversal's instructions differently
+    int32_t* tri;
+    float *t, *b1, *b2;    // each may be null
+    __host__ __device__ void operator()(int64_t i) const {
+        float ray[8];
+        nerfhip::load_ray(rays, i, ray);
+        const MeshHit h = nerfhip::mesh_cast_ray(b, ray);
+        tri[i] = h.tri;
+        if (t) t[i] = h.t;
+        if (b1) b1[i] = h.b1;
+        if (b2) b2[i] = h.b2;
+    }
+};
+
 __global__ void __launch_bounds__(kBlock) mesh_cast(const float4* __restrict__ rays, int64_t n, MeshBvh b, int32_t* __restrict__ tri,
                                                     float* __restrict__ t, float* __restrict__ b1, float* __restrict__ b2) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 a = rays[2 * i], c = rays[2 * i + 1];
-    const float ray[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-    const MeshHit h = nerfhip::mesh_cast_ray(b, ray);
-    tri[i] = h.tri;
-    if (t) t[i] = h.t;
-    if (b1) b1[i] = h.b1;
-    if (b2) b2[i] = h.b2;
+    const int64_t i = nerfhip::item_index();
+    if (i < n) CastItem{rays, b, tri, t, b1, b2}(i);
 }
+
+struct ShadeItem {
+    const float* rays;
+    const int32_t* tri;
+    const float *b1, *b2, *vertices;
+    int64_t V;
+    const int32_t* triangles;
+    int64_t T;
+    const uint8_t* colors;    // may be null
+    float* rgb;               // the pointers in front of the scalars: with rgb behind them hipcc keeps that tail of the struct in LDS
+    float ambient, background;
+    __host__ __device__ void operator()(int64_t i) const {
+        float out[3];
+        nerfhip::mesh_shade_ray(rays + 8 * i, tri[i], b1[i], b2[i], vertices, V, triangles, T, colors, ambient, background, out);
+        rgb[3 * i] = out[0];
+        rgb[3 * i + 1] = out[1];
+        rgb[3 * i + 2] = out[2];
+    }
+};
 
 __global__ void __launch_bounds__(kBlock) mesh_shade(const float* __restrict__ rays, int64_t n, const int32_t* __restrict__ tri,
                                                      const float* __restrict__ b1, const float* __restrict__ b2,
                                                      const float* __restrict__ vertices, int64_t V, const int32_t* __restrict__ triangles,
                                                      int64_t T, const uint8_t* __restrict__ colors, float ambient, float background,
                                                      float* __restrict__ rgb) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float out[3];
-    nerfhip::mesh_shade_ray(rays + 8 * i, tri[i], b1[i], b2[i], vertices, V, triangles, T, colors, ambient, background, out);
-    rgb[3 * i] = out[0];
-    rgb[3 * i + 1] = out[1];
-    rgb[3 * i + 2] = out[2];
+    const int64_t i = nerfhip::item_index();
+    if (i < n) ShadeItem{rays, tri, b1, b2, vertices, V, triangles, T, colors, rgb, ambient, background}(i);
 }
+
+struct ComposeItem {
+    int mode;
+    const float *rgb_n, *depth_n, *opacity_n;
+    const int32_t* tri;
+    const float *t, *rgb_m;
+    float tau, background;
+    float *rgb, *depth, *opacity;
+    uint8_t* mask;    // may be null
+    __host__ __device__ void operator()(int64_t i) const {
+        const MixedPixel px = nerfhip::mixed_compose_ray(mode, rgb_n + 3 * i, depth_n[i], opacity_n[i], tri[i], t[i], rgb_m + 3 * i, tau, background);
+        rgb[3 * i] = px.rgb[0];
+        rgb[3 * i + 1] = px.rgb[1];
+        rgb[3 * i + 2] = px.rgb[2];
+        depth[i] = px.depth;
+        opacity[i] = px.opacity;
+        if (mask) mask[i] = px.mask;
+    }
+};
 
 __global__ void __launch_bounds__(kBlock) mixed_compose(int mode, int64_t n, const float* __restrict__ rgb_n, const float* __restrict__ depth_n,
                                                         const float* __restrict__ opacity_n, const int32_t* __restrict__ tri,
                                                         const float* __restrict__ t, const float* __restrict__ rgb_m, float tau,
                                                         float background, float* __restrict__ rgb, float* __restrict__ depth,
                                                         float* __restrict__ opacity, uint8_t* __restrict__ mask) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const MixedPixel px = nerfhip::mixed_compose_ray(mode, rgb_n + 3 * i, depth_n[i], opacity_n[i], tri[i], t[i], rgb_m + 3 * i, tau, background);
-    rgb[3 * i] = px.rgb[0];
-    rgb[3 * i + 1] = px.rgb[1];
-    rgb[3 * i + 2] = px.rgb[2];
-    depth[i] = px.depth;
-    opacity[i] = px.opacity;
-    if (mask) mask[i] = px.mask;
+    const int64_t i = nerfhip::item_index();
+    if (i < n) ComposeItem{mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background, rgb, depth, opacity, mask}(i);
 }
 
 inline int cast_args(const float* rays, int64_t n, const float* tris, const float* boxes, int64_t T, int brute, const int32_t* tri,
@@ -180,7 +215,7 @@ inline int cast_args(const float* rays, int64_t n, const float* tris, const floa
 inline int shade_args(const float* rays, int64_t n, const int32_t* tri, const float* b1, const float* b2, const float* vertices, int64_t V,
                       const int32_t* triangles, int64_t T, float ambient, float background, const float* rgb) {
     NERFHIP_CHECK_ARG(n >= 0 && n <= kMaxRays && T >= 0 && T <= nerfhip::kMeshMaxTriangles && V >= 0 && V <= kMaxVertices);
-    NERFHIP_CHECK_ARG(ambient >= 0.0f && ambient <= 1.0f && nerfhip::mesh_finite(background));
+    NERFHIP_CHECK_ARG(ambient >= 0.0f && ambient <= 1.0f && nerfhip::finite_f32(background));
     if (n == 0) return 0;
     NERFHIP_CHECK_ARG(rays && tri && b1 && b2 && rgb);
     NERFHIP_CHECK_ARG((T == 0 || triangles) && (V == 0 || vertices));
@@ -194,7 +229,7 @@ inline int compose_args(int mode, int64_t n, const float* rgb_n, const float* de
                         const float* t, const float* rgb_m, float tau, float background, const float* rgb, const float* depth,
                         const float* opacity) {
     NERFHIP_CHECK_ARG((mode == nerfhip::kMixedZtest || mode == nerfhip::kMixedClip) && n >= 0 && n <= kMaxRays);
-    NERFHIP_CHECK_ARG(tau > 0.0f && nerfhip::mesh_finite(tau) && nerfhip::mesh_finite(background));
+    NERFHIP_CHECK_ARG(tau > 0.0f && nerfhip::finite_f32(tau) && nerfhip::finite_f32(background));
     if (n == 0) return 0;
     NERFHIP_CHECK_ARG(rgb_n && depth_n && opacity_n && tri && t && rgb_m && rgb && depth && opacity);
     if (misaligned(rgb_n, 4) || misaligned(depth_n, 4) || misaligned(opacity_n, 4) || misaligned(tri, 4) || misaligned(t, 4) ||
@@ -232,7 +267,7 @@ extern "C" int nerfhip_mesh_bvh_keys_host(const float* vertices, int64_t V, cons
     if (e) return e;
     NERFHIP_CHECK_ARG(state && (keys || T == 0));
     if (misaligned(keys, 8) || misaligned(state, 4)) return NERFHIP_E_ALIGN;
-    const float inf = nerfhip::mesh_from_bits(0x7f800000u);
+    const float inf = nerfhip::float_from_bits(0x7f800000u);
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf}, p[9];
     int32_t bad = 0;
     for (int64_t t = 0; t < T; ++t) {
@@ -312,13 +347,7 @@ extern "C" int nerfhip_mesh_cast_host(const float* rays, int64_t n, const float*
     const int e = cast_args(rays, n, tris, boxes, T, brute, tri, t, b1, b2);
     if (e || n == 0) return e;
     const MeshBvh b = bvh_of(tris, brute ? nullptr : boxes, T);
-    for (int64_t i = 0; i < n; ++i) {
-        const MeshHit h = nerfhip::mesh_cast_ray(b, rays + 8 * i);
-        tri[i] = h.tri;
-        if (t) t[i] = h.t;
-        if (b1) b1[i] = h.b1;
-        if (b2) b2[i] = h.b2;
-    }
+    nerfhip::host_items(n, CastItem{(const float4*)rays, b, tri, t, b1, b2});
     return 0;
 }
 
@@ -337,8 +366,7 @@ extern "C" int nerfhip_mesh_shade_host(const float* rays, int64_t n, const int32
                                        float ambient, float background, float* rgb) {
     const int e = shade_args(rays, n, tri, b1, b2, vertices, V, triangles, T, ambient, background, rgb);
     if (e || n == 0) return e;
-    for (int64_t i = 0; i < n; ++i)
-        nerfhip::mesh_shade_ray(rays + 8 * i, tri[i], b1[i], b2[i], vertices, V, triangles, T, colors_or_null, ambient, background, rgb + 3 * i);
+    nerfhip::host_items(n, ShadeItem{rays, tri, b1, b2, vertices, V, triangles, T, colors_or_null, rgb, ambient, background});
     return 0;
 }
 
@@ -357,15 +385,6 @@ extern "C" int nerfhip_mixed_compose_host(int mode, int64_t n, const float* rgb_
                                           float* depth, float* opacity, uint8_t* mask_or_null) {
     const int e = compose_args(mode, n, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background, rgb, depth, opacity);
     if (e || n == 0) return e;
-    for (int64_t i = 0; i < n; ++i) {
-        const MixedPixel px =
-            nerfhip::mixed_compose_ray(mode, rgb_n + 3 * i, depth_n[i], opacity_n[i], tri[i], t[i], rgb_m + 3 * i, tau, background);
-        rgb[3 * i] = px.rgb[0];
-        rgb[3 * i + 1] = px.rgb[1];
-        rgb[3 * i + 2] = px.rgb[2];
-        depth[i] = px.depth;
-        opacity[i] = px.opacity;
-        if (mask_or_null) mask_or_null[i] = px.mask;
-    }
+    nerfhip::host_items(n, ComposeItem{mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background, rgb, depth, opacity, mask_or_null});
     return 0;
 }

@@ -10,19 +10,20 @@
 #include "block_scan.h"
 #include "common.h"
 #include "occupancy_core.h"
+#include "twin_launch.h"
 
 namespace {
 
 using nerfhip::block_excl_scan;
+using nerfhip::blocks_of;
 using nerfhip::carve;
+using nerfhip::kMaxRays;
+using nerfhip::misaligned;
 using nerfhip::OccGrid;
 using nerfhip::OccVerdict;
 
-constexpr int kBlock = 256;
+constexpr int kBlock = nerfhip::kItemBlock;
 constexpr int kMaxN = 1025;            // M <= 1024: a cell's bit index fits 30 bits
-constexpr int64_t kMaxRays = (int64_t)1 << 30;
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 // ---- bitfield -----------------------------------------------------------------------------------------------------------------
 struct BuildWs {
@@ -80,16 +81,25 @@ __global__ void __launch_bounds__(kBlock) occ_pack(const uint8_t* __restrict__ c
 }
 
 // ---- cull ---------------------------------------------------------------------------------------------------------------------
+struct CullItem {
+    const float4* rays;
+    OccGrid g;
+    uint8_t* hit;
+    float *t0, *t1;
+    __host__ __device__ void operator()(int64_t i) const {
+        float ray[8];
+        nerfhip::load_ray(rays, i, ray);
+        const OccVerdict v = nerfhip::occ_cull_ray(g, ray);
+        hit[i] = v.hit;
+        t0[i] = v.t0;
+        t1[i] = v.t1;
+    }
+};
+
 __global__ void __launch_bounds__(kBlock) cull_rays(const float4* __restrict__ rays, int64_t n, OccGrid g, uint8_t* __restrict__ hit,
                                                     float* __restrict__ t0, float* __restrict__ t1) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 a = rays[2 * i], b = rays[2 * i + 1];
-    const float ray[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const OccVerdict v = nerfhip::occ_cull_ray(g, ray);
-    hit[i] = v.hit;
-    t0[i] = v.t0;
-    t1[i] = v.t1;
+    const int64_t i = nerfhip::item_index();
+    if (i < n) CullItem{rays, g, hit, t0, t1}(i);
 }
 
 // M >= 1, lo < hi on every axis, everything finite; fills g (words stay the caller's)
@@ -99,11 +109,11 @@ inline bool make_grid(const void* words, int M, const float* ranges, OccGrid& g)
     g.M = M;
     for (int a = 0; a < 3; ++a) {
         const float lo = ranges[2 * a], hi = ranges[2 * a + 1];
-        if (!(lo < hi) || !(fabsf(lo) <= 3.402823466e+38f) || !(fabsf(hi) <= 3.402823466e+38f)) return false;
+        if (!(lo < hi) || !nerfhip::finite_f32(lo) || !nerfhip::finite_f32(hi)) return false;
         g.lo[a] = lo;
         g.hi[a] = hi;
         g.h[a] = (hi - lo) / (float)M;
-        if (!(g.h[a] > 0.0f) || !(g.h[a] <= 3.402823466e+38f)) return false;
+        if (!(g.h[a] > 0.0f) || !nerfhip::finite_f32(g.h[a])) return false;
     }
     return true;
 }
@@ -114,7 +124,7 @@ inline int cull_args(const float* rays, int64_t n, const int32_t* words, int M, 
     NERFHIP_CHECK_ARG(make_grid(words, M, ranges, g));
     if (n == 0) return 0;
     NERFHIP_CHECK_ARG(rays && words && hit && t0 && t1);
-    if ((((uintptr_t)rays) & 15) || (((uintptr_t)words) & 3) || ((((uintptr_t)t0) | ((uintptr_t)t1)) & 3)) return NERFHIP_E_ALIGN;
+    if (misaligned(rays, 16) || misaligned(words, 4) || misaligned(t0, 4) || misaligned(t1, 4)) return NERFHIP_E_ALIGN;
     return 0;
 }
 
@@ -203,7 +213,7 @@ extern "C" size_t nerfhip_occupancy_workspace_bytes(int N) {
 extern "C" int nerfhip_occupancy_build(const float* sigma, int N, float threshold, int dilate, int32_t* words, void* workspace,
                                        nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(N >= 2 && N <= kMaxN && dilate >= 0 && sigma && words && workspace);
-    if ((((uintptr_t)sigma) & 3) || (((uintptr_t)words) & 3)) return NERFHIP_E_ALIGN;
+    if (misaligned(sigma, 4) || misaligned(words, 4)) return NERFHIP_E_ALIGN;
     const int M = N - 1;
     const uint32_t n_cells = (uint32_t)M * M * M, n_words = (n_cells + 31) / 32;
     const BuildWs w = build_ws(workspace, M, nullptr);
@@ -235,12 +245,7 @@ extern "C" int nerfhip_cull_rays_host(const float* rays, int64_t n, const int32_
     OccGrid g;
     const int e = cull_args(rays, n, words, M, ranges_host, hit, t0, t1, g);
     if (e || n == 0) return e;
-    for (int64_t i = 0; i < n; ++i) {
-        const OccVerdict v = nerfhip::occ_cull_ray(g, rays + 8 * i);
-        hit[i] = v.hit;
-        t0[i] = v.t0;
-        t1[i] = v.t1;
-    }
+    nerfhip::host_items(n, CullItem{(const float4*)rays, g, hit, t0, t1});
     return 0;
 }
 
@@ -254,7 +259,7 @@ extern "C" size_t nerfhip_cull_compact_workspace_bytes(int64_t n) {
 extern "C" int nerfhip_cull_compact(const uint8_t* hit, const float* rays, const float* t0, const float* t1, int64_t n, int32_t* slot,
                                     int32_t* index, float* rays_out, int32_t* n_hit, void* workspace, nerfhip_stream_t stream) {
     NERFHIP_CHECK_ARG(n >= 0 && n <= kMaxRays && n_hit);
-    if (((uintptr_t)n_hit) & 3) return NERFHIP_E_ALIGN;
+    if (misaligned(n_hit, 4)) return NERFHIP_E_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
         CompactWs none{nullptr, nullptr};
@@ -262,8 +267,8 @@ extern "C" int nerfhip_cull_compact(const uint8_t* hit, const float* rays, const
         return nerfhip_launch_status();
     }
     NERFHIP_CHECK_ARG(hit && rays && slot && index && rays_out && workspace);
-    if (((((uintptr_t)rays) | ((uintptr_t)rays_out)) & 15) || (((uintptr_t)workspace) & 7) ||
-        ((((uintptr_t)t0) | ((uintptr_t)t1) | ((uintptr_t)slot) | ((uintptr_t)index)) & 3))
+    if (misaligned(rays, 16) || misaligned(rays_out, 16) || misaligned(workspace, 8) || misaligned(t0, 4) || misaligned(t1, 4) ||
+        misaligned(slot, 4) || misaligned(index, 4))
         return NERFHIP_E_ALIGN;
     const CompactWs w = compact_ws(workspace, n, nullptr);
     const unsigned nb = blocks_of(n);
@@ -284,7 +289,7 @@ extern "C" int nerfhip_cull_scatter(const int32_t* slot, int64_t n, int64_t n_co
     // an output without its compact source is refused unless nothing was rendered (then every row is the background)
     NERFHIP_CHECK_ARG(!(rgb_out && !rgb && n_compact > 0));
     for (int k = 0; k < 3; ++k) NERFHIP_CHECK_ARG(!(a.scalar_out[k] && !a.scalar[k] && n_compact > 0));
-    if (((uintptr_t)slot) & 3) return NERFHIP_E_ALIGN;
+    if (misaligned(slot, 4)) return NERFHIP_E_ALIGN;
     hipLaunchKernelGGL(cull_scatter, dim3(blocks_of(n)), dim3(kBlock), 0, (hipStream_t)stream, slot, n, n_compact,
                        white_back ? 1.0f : 0.0f, a);
     return nerfhip_launch_status();

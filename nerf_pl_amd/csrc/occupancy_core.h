@@ -6,14 +6,7 @@
 // occupied cell and from the back until the last.  A cell's planes are formed from its index at every step (lo + i h, the last
 // one `hi` itself), never accumulated, so the error of a crossing parameter is that of one (p - o) / d whatever the grid size.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define NH_OCC_HD __host__ __device__ inline
-#else
-#define NH_OCC_HD inline
-#endif
+#include "twin.h"
 
 namespace nerfhip {
 
@@ -29,26 +22,24 @@ struct OccVerdict {
     uint8_t hit;
 };
 
-NH_OCC_HD bool occ_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }    // false for NaN and +-inf
-
-NH_OCC_HD bool occ_bit(const OccGrid& g, int ix, int iy, int iz) {
+NH_TWIN_HD bool occ_bit(const OccGrid& g, int ix, int iy, int iz) {
     const uint32_t c = ((uint32_t)iy * (uint32_t)g.M + (uint32_t)ix) * (uint32_t)g.M + (uint32_t)iz;
     return (g.words[c >> 5] >> (c & 31)) & 1u;
 }
 
 // The plane with index i (0 .. M) of axis a.
-NH_OCC_HD float occ_plane(const OccGrid& g, int a, int i) { return i == g.M ? g.hi[a] : g.lo[a] + (float)i * g.h[a]; }
+NH_TWIN_HD float occ_plane(const OccGrid& g, int a, int i) { return i == g.M ? g.hi[a] : g.lo[a] + (float)i * g.h[a]; }
 
 // The cell of axis a that holds coordinate p, clamped into the grid (a point on the upper face belongs to the last cell; a NaN
 // or an overflowed p cannot leave the range).
-NH_OCC_HD int occ_cell(const OccGrid& g, int a, float p) {
+NH_TWIN_HD int occ_cell(const OccGrid& g, int a, float p) {
     const float f = floorf((p - g.lo[a]) / g.h[a]);
     return (int)fminf(fmaxf(f, 0.0f), (float)(g.M - 1));
 }
 
 // Move the index of axis `ax` one cell along (dir = 1) or against (dir = -1) the ray; false when that leaves the grid.  Written
 // as selects over the three axes so that the indices stay in registers.
-NH_OCC_HD bool occ_step(int* i, const float* d, int ax, int dir, int M) {
+NH_TWIN_HD bool occ_step(int* i, const float* d, int ax, int dir, int M) {
     bool inside = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -59,36 +50,18 @@ NH_OCC_HD bool occ_step(int* i, const float* d, int ax, int dir, int M) {
     return inside;
 }
 
-NH_OCC_HD OccVerdict occ_cull_ray(const OccGrid& g, const float* __restrict__ ray) {
-    float o[3], d[3];
-    const float near = ray[6], far = ray[7];
-    bool finite = occ_finite(near) && occ_finite(far);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        o[a] = ray[a];
-        d[a] = ray[3 + a];
-        finite = finite && occ_finite(o[a]) && occ_finite(d[a]);
-    }
+NH_TWIN_HD OccVerdict occ_cull_ray(const OccGrid& g, const float* __restrict__ ray) {
+    const RayRow r = ray_row(ray);
+    const float* o = r.o;
+    const float* d = r.d;
     OccVerdict v;
-    v.t0 = near;
-    v.t1 = far;
+    v.t0 = r.near;
+    v.t1 = r.far;
     v.hit = 1;
-    if (!finite) return v;           // culling never decides what it cannot reason about
+    if (!r.finite) return v;         // culling never decides what it cannot reason about
     v.hit = 0;
-
-    // clip [near, far] to the box; a zero component (either sign) leaves the interval alone or misses, and never divides
-    float tmin = near, tmax = far;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (d[a] == 0.0f) {
-            if (o[a] < g.lo[a] || o[a] > g.hi[a]) return v;
-            continue;
-        }
-        const float ta = (g.lo[a] - o[a]) / d[a], tb = (g.hi[a] - o[a]) / d[a];
-        tmin = fmaxf(tmin, fminf(ta, tb));
-        tmax = fminf(tmax, fmaxf(ta, tb));
-    }
-    if (!(tmin < tmax)) return v;
+    float tmin, tmax;
+    if (!ray_clip_box(r, g.lo, g.hi, tmin, tmax)) return v;
 
     const int M = g.M;
     const int budget = 3 * M + 3;    // a walk changes one index by one per step and never turns back

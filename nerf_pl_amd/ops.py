@@ -1615,6 +1615,82 @@ def _same_device(what, *tensors):
         raise NerfHipError("%s: tensors of one call live on different GPUs (%s)" % (what, ", ".join(sorted(str(d) for d in devs))))
 
 
+def _np16(a, dtype):
+    """a C-contiguous numpy array of `dtype` whose data is 16-byte aligned, as device buffers are"""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype)
+    if a.ctypes.data & 15:
+        buf = np.empty(a.nbytes + 16, np.uint8)
+        off = (-buf.ctypes.data) & 15
+        out = buf[off:off + a.nbytes].view(dtype).reshape(a.shape)
+        out[...] = a
+        a = out
+    return a
+
+
+class _DeviceArrays:
+    """The arrays of a device call: tensors on one GPU.  A ray unit's device wrapper and its _host twin share one body (the
+    `_name(B, ...)` functions below) written against this and `_HostArrays`; dtypes are named as numpy names them."""
+    suffix = ""
+
+    @staticmethod
+    def array(what, name, a, dtype, tail=None):
+        """`a` as the call reads it: (n,) + tail of `dtype` (tail None: any shape).  NerfHipError for anything else."""
+        return _require_dev(what, name, a, getattr(torch, dtype), tail)
+
+    same_device = staticmethod(_same_device)
+
+    @staticmethod
+    def empty(like, shape, dtype):
+        return torch.empty(shape, device=like.device, dtype=getattr(torch, dtype))
+
+    ptr = staticmethod(ptr)
+
+    @staticmethod
+    def sort(keys):
+        return torch.sort(keys)[0]
+
+    @staticmethod
+    def call(name, *args):
+        check(getattr(_lib.load(), name)(*args, stream_ptr()), name)
+
+
+class _HostArrays:
+    """The arrays of a _host call: numpy, 16-byte aligned as device buffers are."""
+    suffix = "_host"
+
+    @staticmethod
+    def array(what, name, a, dtype, tail=None):
+        a = _np16(a, dtype)
+        if tail is not None and (a.ndim != 1 + len(tail) or a.shape[1:] != tail):
+            raise ValueError("%s: %s must be (n%s), got %s" % (what, name, "".join(", %d" % s for s in tail), a.shape))
+        return a
+
+    same_device = staticmethod(lambda what, *arrays: None)
+
+    @staticmethod
+    def empty(like, shape, dtype):
+        import numpy as np
+        return _np16(np.zeros(shape, dtype), dtype)
+
+    @staticmethod
+    def ptr(a):
+        return None if a is None else a.ctypes.data
+
+    @staticmethod
+    def sort(keys):
+        import numpy as np
+        return _np16(np.sort(keys), keys.dtype)
+
+    @staticmethod
+    def call(name, *args):
+        check(getattr(_lib.load(), name + "_host")(*args), name + "_host")
+
+
+def _numel(a):
+    return a.numel() if torch.is_tensor(a) else a.size
+
+
 @device_guard
 def occupancy_build(sigma, threshold=0.0, dilate=1):
     """nerfhip_occupancy_build: sigma (N, N, N) fp32 on the device, indexed [iy, ix, iz] (grid.sigma_grid) -> the bitfield of its
@@ -1636,42 +1712,34 @@ def occupancy_build(sigma, threshold=0.0, dilate=1):
 def _cull_grid_args(what, words, M, ranges):
     """`words` (a tensor or an array) must hold the whole grid: a short one would be an out-of-bounds read, not an error."""
     M = int(M)
-    have = words.numel() if torch.is_tensor(words) else words.size
-    if 1 <= M < OCCUPANCY_MAX_N and have < occupancy_words(M):
-        raise ValueError("%s: %d words for a grid of %d^3 cells (needs %d)" % (what, have, M, occupancy_words(M)))
+    if 1 <= M < OCCUPANCY_MAX_N and _numel(words) < occupancy_words(M):
+        raise ValueError("%s: %d words for a grid of %d^3 cells (needs %d)" % (what, _numel(words), M, occupancy_words(M)))
     return M, _ranges_arg(what, ranges)
+
+
+def _cull_rays(B, rays, words, M, ranges):
+    what = "cull_rays" + B.suffix
+    rays = B.array(what, "rays", rays, "float32", (8,))
+    words = B.array(what, "words", words, "int32")
+    B.same_device(what, rays, words)
+    M, rg = _cull_grid_args(what, words, M, ranges)
+    n = rays.shape[0]
+    hit, t0, t1 = B.empty(rays, n, "uint8"), B.empty(rays, n, "float32"), B.empty(rays, n, "float32")
+    B.call("nerfhip_cull_rays", B.ptr(rays), n, B.ptr(words), M, rg, B.ptr(hit), B.ptr(t0), B.ptr(t1))
+    return hit, t0, t1
 
 
 @device_guard
 def cull_rays(rays, words, M, ranges):
     """nerfhip_cull_rays: rays (n, 8) fp32 against the bitfield `words` of an M^3 grid over `ranges` -> (hit (n,) uint8,
     t0 (n,), t1 (n,)) on the device."""
-    rays = _require_dev("cull_rays", "rays", rays, torch.float32, (8,))
-    words = _require_dev("cull_rays", "words", words, torch.int32)
-    _same_device("cull_rays", rays, words)
-    M, rg = _cull_grid_args("cull_rays", words, M, ranges)
-    n = rays.shape[0]
-    hit = torch.empty(n, device=rays.device, dtype=torch.uint8)
-    t0 = torch.empty(n, device=rays.device, dtype=torch.float32)
-    t1 = torch.empty(n, device=rays.device, dtype=torch.float32)
-    check(_lib.load().nerfhip_cull_rays(ptr(rays), n, ptr(words), M, rg, ptr(hit), ptr(t0), ptr(t1), stream_ptr()), "nerfhip_cull_rays")
-    return hit, t0, t1
+    return _cull_rays(_DeviceArrays, rays, words, M, ranges)
 
 
 def cull_rays_host(rays, words, M, ranges):
     """nerfhip_cull_rays_host (host, no GPU): numpy rays (n, 8) float32 and int32 words -> numpy (hit, t0, t1), by the kernel's
     own per-ray routine.  For tests of the traversal on a machine without a GPU."""
-    import numpy as np
-    rays = np.ascontiguousarray(rays, np.float32)
-    words = np.ascontiguousarray(words, np.int32)
-    if rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError("cull_rays_host: rays must be (n, 8), got %s" % (rays.shape,))
-    M, rg = _cull_grid_args("cull_rays_host", words, M, ranges)
-    n = rays.shape[0]
-    hit, t0, t1 = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.float32)
-    check(_lib.load().nerfhip_cull_rays_host(rays.ctypes.data, n, words.ctypes.data, M, rg, hit.ctypes.data, t0.ctypes.data,
-                                             t1.ctypes.data), "nerfhip_cull_rays_host")
-    return hit, t0, t1
+    return _cull_rays(_HostArrays, rays, words, M, ranges)
 
 
 @device_guard
@@ -1809,10 +1877,10 @@ def baked_from_dense(rgba):
     return data
 
 
-def _baked_data(what, data, N):
-    data = _require_dev(what, "data", data, torch.uint8, ())
-    if data.numel() != baked_bytes(N):
-        raise ValueError("%s: the bricked volume of a %d^3 lattice has %d bytes, got %d" % (what, N, baked_bytes(N), data.numel()))
+def _baked_data(what, data, N, B=_DeviceArrays):
+    data = B.array(what, "data", data, "uint8", ())
+    if _numel(data) != baked_bytes(N):
+        raise ValueError("%s: the bricked volume of a %d^3 lattice has %d bytes, got %d" % (what, N, baked_bytes(N), _numel(data)))
     return data
 
 
@@ -1826,56 +1894,38 @@ def baked_bricks(data, N):
     return words
 
 
+def _baked_render(B, rays, data, bits, N, ranges, cell, step, t_stop, white_back):
+    what = "baked_render" + B.suffix
+    N = _baked_N(what, N)
+    rays = B.array(what, "rays", rays, "float32", (8,))
+    data = _baked_data(what, data, N, B)
+    if bits is not None:
+        bits = B.array(what, "bits", bits, "int32", ())
+        if _numel(bits) < baked_brick_words(N):
+            raise ValueError("%s: %d words for the bricks of a %d^3 lattice (needs %d)" % (what, _numel(bits), N, baked_brick_words(N)))
+    B.same_device(what, rays, data, bits)
+    rg = _ranges_arg(what, ranges)
+    n = rays.shape[0]
+    rgb, depth, opacity = B.empty(rays, (n, 3), "float32"), B.empty(rays, n, "float32"), B.empty(rays, n, "float32")
+    B.call("nerfhip_baked_render", B.ptr(rays), n, B.ptr(data), B.ptr(bits), N, rg, float(cell), float(step), float(t_stop),
+           int(bool(white_back)), B.ptr(rgb), B.ptr(depth), B.ptr(opacity))
+    return rgb, depth, opacity
+
+
 @device_guard
 def baked_render(rays, data, bits, N, ranges, cell, step=0.5, t_stop=0.0, white_back=False):
     """nerfhip_baked_render: rays (n, 8) fp32 marched through the bricked volume `data` of an N^3 lattice over `ranges` ->
     (rgb (n, 3), depth (n,), opacity (n,)) on the device.  bits: the cell-brick bitfield, or None (no skipping; the same bits
     of output)."""
-    N = _baked_N("baked_render", N)
-    rays = _require_dev("baked_render", "rays", rays, torch.float32, (8,))
-    data = _baked_data("baked_render", data, N)
-    if bits is not None:
-        bits = _require_dev("baked_render", "bits", bits, torch.int32, ())
-        if bits.numel() < baked_brick_words(N):
-            raise ValueError("baked_render: %d words for the bricks of a %d^3 lattice (needs %d)" % (bits.numel(), N, baked_brick_words(N)))
-    _same_device("baked_render", rays, data, bits)
-    rg = _ranges_arg("baked_render", ranges)
-    n = rays.shape[0]
-    rgb = torch.empty(n, 3, device=rays.device, dtype=torch.float32)
-    depth = torch.empty(n, device=rays.device, dtype=torch.float32)
-    opacity = torch.empty(n, device=rays.device, dtype=torch.float32)
-    check(_lib.load().nerfhip_baked_render(ptr(rays), n, ptr(data), ptr(bits), N, rg, float(cell), float(step), float(t_stop),
-                                           int(bool(white_back)), ptr(rgb), ptr(depth), ptr(opacity), stream_ptr()), "nerfhip_baked_render")
-    return rgb, depth, opacity
+    return _baked_render(_DeviceArrays, rays, data, bits, N, ranges, cell, step, t_stop, white_back)
 
 
 def baked_render_host(rays, data, bits, N, ranges, cell, step=0.5, t_stop=0.0, white_back=False):
     """nerfhip_baked_render_host (host, no GPU): numpy rays (n, 8) float32, the bricked volume as a uint8 array and the bitfield
     as int32 words (or None) -> numpy (rgb, depth, opacity), by the kernel's own per-ray routine."""
     import numpy as np
-    N = _baked_N("baked_render_host", N)
-    rays = np.ascontiguousarray(rays, np.float32)
-    if rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError("baked_render_host: rays must be (n, 8), got %s" % (rays.shape,))
-    data = np.ascontiguousarray(data, np.uint8).ravel()
-    if data.size != baked_bytes(N):
-        raise ValueError("baked_render_host: the bricked volume of a %d^3 lattice has %d bytes, got %d" % (N, baked_bytes(N), data.size))
-    if data.ctypes.data & 15:                             # the entry point wants the 16-byte alignment device buffers have
-        buf = np.empty(data.size + 16, np.uint8)
-        off = (-buf.ctypes.data) & 15
-        buf[off:off + data.size] = data
-        data = buf[off:off + data.size]
-    if bits is not None:
-        bits = np.ascontiguousarray(bits, np.int32)
-        if bits.size < baked_brick_words(N):
-            raise ValueError("baked_render_host: %d words for the bricks of a %d^3 lattice (needs %d)" % (bits.size, N, baked_brick_words(N)))
-    rg = _ranges_arg("baked_render_host", ranges)
-    n = rays.shape[0]
-    rgb, depth, opacity = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
-    check(_lib.load().nerfhip_baked_render_host(rays.ctypes.data, n, data.ctypes.data, None if bits is None else bits.ctypes.data, N, rg,
-                                                float(cell), float(step), float(t_stop), int(bool(white_back)), rgb.ctypes.data,
-                                                depth.ctypes.data, opacity.ctypes.data), "nerfhip_baked_render_host")
-    return rgb, depth, opacity
+    data, bits = (None if a is None else np.asarray(a).ravel() for a in (data, bits))      # of any shape
+    return _baked_render(_HostArrays, rays, data, bits, N, ranges, cell, step, t_stop, white_back)
 
 
 # ---- ray casting against a triangle mesh (csrc/meshcast.hip, DESIGN.md §20) -------------------------------------------------------
@@ -1903,15 +1953,25 @@ def mesh_bvh_nodes(T):
     return levels[-1][0] + levels[-1][1] if levels else 0
 
 
-def _mesh_arrays(what, vertices, triangles):
-    vertices = _require_dev(what, "vertices", vertices, torch.float32, (3,))
-    triangles = _require_dev(what, "triangles", triangles, torch.int32, (3,))
-    if vertices.dim() != 2 or triangles.dim() != 2:
-        raise NerfHipError("%s: vertices must be (V, 3) and triangles (T, 3)" % what)
+def _mesh_arrays(B, what, vertices, triangles):
+    vertices = B.array(what, "vertices", vertices, "float32", (3,))
+    triangles = B.array(what, "triangles", triangles, "int32", (3,))
     if triangles.shape[0] > MESH_MAX_TRIANGLES:
         raise ValueError("%s: at most 2^28 triangles, got %d" % (what, triangles.shape[0]))
-    _same_device(what, vertices, triangles)
+    B.same_device(what, vertices, triangles)
     return vertices, triangles
+
+
+def _mesh_bvh_build(B, vertices, triangles):
+    what = "mesh_bvh_build" + B.suffix
+    vertices, triangles = _mesh_arrays(B, what, vertices, triangles)
+    V, T = vertices.shape[0], triangles.shape[0]
+    keys, state = B.empty(vertices, T, "int64"), B.empty(vertices, 8, "int32")
+    B.call("nerfhip_mesh_bvh_keys", B.ptr(vertices), V, B.ptr(triangles), T, B.ptr(keys), B.ptr(state))
+    sorted_keys = B.sort(keys)
+    tris, boxes = B.empty(vertices, (T, 12), "float32"), B.empty(vertices, (mesh_bvh_nodes(T), 6), "float32")
+    B.call("nerfhip_mesh_bvh_boxes", B.ptr(vertices), V, B.ptr(triangles), T, B.ptr(sorted_keys), B.ptr(tris), B.ptr(boxes))
+    return tris, boxes, sorted_keys & 0xffffffff, state[:1]
 
 
 @device_guard
@@ -1920,123 +1980,67 @@ def mesh_bvh_build(vertices, triangles):
     (tris (T, 12) fp32: the sorted triangles' vertices with their original numbers; boxes (mesh_bvh_nodes(T), 6) fp32; order (T,)
     int32: the original number of every sorted triangle; n_bad (1,) int32 on the device: triangles with an index outside [0, V) or a
     non-finite coordinate, which no cast returns).  The keys are distinct, so the sort decides nothing."""
-    vertices, triangles = _mesh_arrays("mesh_bvh_build", vertices, triangles)
-    dev = vertices.device
-    V, T = vertices.shape[0], triangles.shape[0]
-    lib = _lib.load()
-    keys = torch.empty(T, device=dev, dtype=torch.int64)
-    state = torch.empty(8, device=dev, dtype=torch.int32)
-    check(lib.nerfhip_mesh_bvh_keys(ptr(vertices), V, ptr(triangles), T, ptr(keys), ptr(state), stream_ptr()), "nerfhip_mesh_bvh_keys")
-    sorted_keys, _ = torch.sort(keys)
-    tris = torch.empty(T, 12, device=dev, dtype=torch.float32)
-    boxes = torch.empty(mesh_bvh_nodes(T), 6, device=dev, dtype=torch.float32)
-    check(lib.nerfhip_mesh_bvh_boxes(ptr(vertices), V, ptr(triangles), T, ptr(sorted_keys), ptr(tris), ptr(boxes), stream_ptr()),
-          "nerfhip_mesh_bvh_boxes")
-    order = (sorted_keys & 0xffffffff).to(torch.int32)
-    return tris, boxes, order, state[:1]
-
-
-def _np16(a, dtype):
-    """a C-contiguous numpy array of `dtype` whose data is 16-byte aligned, as device buffers are"""
-    import numpy as np
-    a = np.ascontiguousarray(a, dtype)
-    if a.ctypes.data & 15:
-        buf = np.empty(a.nbytes + 16, np.uint8)
-        off = (-buf.ctypes.data) & 15
-        out = buf[off:off + a.nbytes].view(dtype).reshape(a.shape)
-        out[...] = a
-        a = out
-    return a
-
-
-def _np_out(shape, dtype):
-    import numpy as np
-    return _np16(np.zeros(shape, dtype), dtype)
-
-
-def _mesh_arrays_host(what, vertices, triangles):
-    import numpy as np
-    vertices, triangles = _np16(vertices, np.float32), _np16(triangles, np.int32)
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or triangles.ndim != 2 or triangles.shape[1] != 3:
-        raise ValueError("%s: vertices must be (V, 3) and triangles (T, 3), got %s and %s" % (what, vertices.shape, triangles.shape))
-    return vertices, triangles
+    tris, boxes, order, n_bad = _mesh_bvh_build(_DeviceArrays, vertices, triangles)
+    return tris, boxes, order.to(torch.int32), n_bad
 
 
 def mesh_bvh_build_host(vertices, triangles):
     """The _host twins of `mesh_bvh_build` with numpy's sort between them (host, no GPU): numpy in, numpy (tris, boxes, order,
     n_bad (1,) int32) out, bit for bit what the device builds."""
     import numpy as np
-    vertices, triangles = _mesh_arrays_host("mesh_bvh_build_host", vertices, triangles)
-    V, T = vertices.shape[0], triangles.shape[0]
-    lib = _lib.load()
-    keys, state = _np_out(T, np.int64), _np_out(8, np.int32)
-    check(lib.nerfhip_mesh_bvh_keys_host(vertices.ctypes.data, V, triangles.ctypes.data, T, keys.ctypes.data, state.ctypes.data),
-          "nerfhip_mesh_bvh_keys_host")
-    sorted_keys = _np16(np.sort(keys), np.int64)
-    tris, boxes = _np_out((T, 12), np.float32), _np_out((mesh_bvh_nodes(T), 6), np.float32)
-    check(lib.nerfhip_mesh_bvh_boxes_host(vertices.ctypes.data, V, triangles.ctypes.data, T, sorted_keys.ctypes.data, tris.ctypes.data,
-                                          boxes.ctypes.data), "nerfhip_mesh_bvh_boxes_host")
-    return tris, boxes, (sorted_keys & 0xffffffff).astype(np.int32), state[:1].copy()
+    tris, boxes, order, n_bad = _mesh_bvh_build(_HostArrays, vertices, triangles)
+    return tris, boxes, order.astype(np.int32), n_bad.copy()
 
 
-def _bvh_arg(what, tris, boxes):
-    tris = _require_dev(what, "tris", tris, torch.float32, (12,))
-    boxes = _require_dev(what, "boxes", boxes, torch.float32, (6,))
-    if boxes.shape[0] != mesh_bvh_nodes(tris.shape[0]):
-        raise ValueError("%s: a hierarchy of %d triangles has %d boxes, got %d" % (what, tris.shape[0], mesh_bvh_nodes(tris.shape[0]),
-                                                                                   boxes.shape[0]))
-    return tris, boxes
+def _mesh_cast(B, rays, tris, boxes, brute=False):
+    what = "mesh_cast" + B.suffix
+    rays = B.array(what, "rays", rays, "float32", (8,))
+    tris = B.array(what, "tris", tris, "float32", (12,))
+    T = tris.shape[0]
+    boxes = None if brute else B.array(what, "boxes", boxes, "float32", (6,))
+    if boxes is not None and boxes.shape[0] != mesh_bvh_nodes(T):
+        raise ValueError("%s: a hierarchy of %d triangles has %d boxes, got %d" % (what, T, mesh_bvh_nodes(T), boxes.shape[0]))
+    B.same_device(what, rays, tris, boxes)
+    n = rays.shape[0]
+    tri, t, b1, b2 = (B.empty(rays, n, dtype) for dtype in ("int32", "float32", "float32", "float32"))
+    only_host = (int(bool(brute)),) if B is _HostArrays else ()
+    B.call("nerfhip_mesh_cast", B.ptr(rays), n, B.ptr(tris), B.ptr(boxes), T, *only_host, B.ptr(tri), B.ptr(t), B.ptr(b1), B.ptr(b2))
+    return tri, t, b1, b2
 
 
 @device_guard
 def mesh_cast(rays, tris, boxes):
     """nerfhip_mesh_cast: rays (n, 8) fp32 against the hierarchy of `mesh_bvh_build` -> (tri (n,) int32: the original number of the
     nearest triangle hit within [near, far], -1 for a miss; t (n,); b1 (n,); b2 (n,)), on the device."""
-    rays = _require_dev("mesh_cast", "rays", rays, torch.float32, (8,))
-    tris, boxes = _bvh_arg("mesh_cast", tris, boxes)
-    _same_device("mesh_cast", rays, tris, boxes)
-    n, dev = rays.shape[0], rays.device
-    tri = torch.empty(n, device=dev, dtype=torch.int32)
-    t, b1, b2 = (torch.empty(n, device=dev, dtype=torch.float32) for _ in range(3))
-    check(_lib.load().nerfhip_mesh_cast(ptr(rays), n, ptr(tris), ptr(boxes), tris.shape[0], ptr(tri), ptr(t), ptr(b1), ptr(b2),
-                                        stream_ptr()), "nerfhip_mesh_cast")
-    return tri, t, b1, b2
-
-
-def _rays_host(what, rays):
-    import numpy as np
-    rays = _np16(rays, np.float32)
-    if rays.ndim != 2 or rays.shape[1] != 8:
-        raise ValueError("%s: rays must be (n, 8), got %s" % (what, rays.shape))
-    return rays
+    return _mesh_cast(_DeviceArrays, rays, tris, boxes)
 
 
 def mesh_cast_host(rays, tris, boxes, brute=False):
     """nerfhip_mesh_cast_host (host, no GPU): numpy rays (n, 8) against a numpy hierarchy -> numpy (tri, t, b1, b2), by the kernel's
     own per-ray routine.  brute=True tests every triangle and reads no box (boxes may be None)."""
-    import numpy as np
-    rays = _rays_host("mesh_cast_host", rays)
-    tris = _np16(tris, np.float32)
-    if tris.ndim != 2 or tris.shape[1] != 12:
-        raise ValueError("mesh_cast_host: tris must be (T, 12), got %s" % (tris.shape,))
-    T = tris.shape[0]
-    if not brute:
-        boxes = _np16(boxes, np.float32)
-        if boxes.shape != (mesh_bvh_nodes(T), 6):
-            raise ValueError("mesh_cast_host: a hierarchy of %d triangles has %d boxes, got %s" % (T, mesh_bvh_nodes(T), boxes.shape))
+    return _mesh_cast(_HostArrays, rays, tris, boxes, brute)
+
+
+def _mesh_shade(B, rays, tri, b1, b2, vertices, triangles, colors, ambient, background):
+    what = "mesh_shade" + B.suffix
+    rays = B.array(what, "rays", rays, "float32", (8,))
+    tri, b1, b2 = B.array(what, "tri", tri, "int32", ()), B.array(what, "b1", b1, "float32", ()), B.array(what, "b2", b2, "float32", ())
+    vertices, triangles = _mesh_arrays(B, what, vertices, triangles)
+    if colors is not None:
+        colors = B.array(what, "colors", colors, "uint8", (3,))
+        if colors.shape[0] != vertices.shape[0]:
+            raise ValueError("%s: %d colours for %d vertices" % (what, colors.shape[0], vertices.shape[0]))
     n = rays.shape[0]
-    tri, t, b1, b2 = _np_out(n, np.int32), _np_out(n, np.float32), _np_out(n, np.float32), _np_out(n, np.float32)
-    check(_lib.load().nerfhip_mesh_cast_host(rays.ctypes.data, n, tris.ctypes.data, None if brute else boxes.ctypes.data, T,
-                                             int(bool(brute)), tri.ctypes.data, t.ctypes.data, b1.ctypes.data, b2.ctypes.data),
-          "nerfhip_mesh_cast_host")
-    return tri, t, b1, b2
-
-
-def _shade_scalars(what, ambient, background):
+    if not tri.shape[0] == b1.shape[0] == b2.shape[0] == n:
+        raise ValueError("%s: tri, b1 and b2 must have one entry per ray" % what)
+    B.same_device(what, rays, tri, b1, b2, vertices, triangles, colors)
     ambient, background = float(ambient), float(background)
     if not 0.0 <= ambient <= 1.0:
         raise ValueError("%s: ambient must be in [0, 1], got %r" % (what, ambient))
-    return ambient, background
+    rgb = B.empty(rays, (n, 3), "float32")
+    B.call("nerfhip_mesh_shade", B.ptr(rays), n, B.ptr(tri), B.ptr(b1), B.ptr(b2), B.ptr(vertices), vertices.shape[0], B.ptr(triangles),
+           triangles.shape[0], B.ptr(colors), ambient, background, B.ptr(rgb))
+    return rgb
 
 
 @device_guard
@@ -2044,55 +2048,33 @@ def mesh_shade(rays, tri, b1, b2, vertices, triangles, colors=None, ambient=1.0,
     """nerfhip_mesh_shade: the hits of `mesh_cast` -> rgb (n, 3): the barycentric blend of the vertex colours (colors (V, 3) uint8 /
     255; None: white) times ambient + (1 - ambient) |n . d|, n the triangle's unit normal and d the unit direction; `background`
     for a miss."""
-    rays = _require_dev("mesh_shade", "rays", rays, torch.float32, (8,))
-    tri = _require_dev("mesh_shade", "tri", tri, torch.int32, ())
-    b1 = _require_dev("mesh_shade", "b1", b1, torch.float32, ())
-    b2 = _require_dev("mesh_shade", "b2", b2, torch.float32, ())
-    vertices, triangles = _mesh_arrays("mesh_shade", vertices, triangles)
-    if colors is not None:
-        colors = _require_dev("mesh_shade", "colors", colors, torch.uint8, (3,))
-        if colors.shape[0] != vertices.shape[0]:
-            raise ValueError("mesh_shade: %d colours for %d vertices" % (colors.shape[0], vertices.shape[0]))
-    n = rays.shape[0]
-    if not tri.shape[0] == b1.shape[0] == b2.shape[0] == n:
-        raise ValueError("mesh_shade: tri, b1 and b2 must have one entry per ray")
-    _same_device("mesh_shade", rays, tri, b1, b2, vertices, triangles, colors)
-    ambient, background = _shade_scalars("mesh_shade", ambient, background)
-    rgb = torch.empty(n, 3, device=rays.device, dtype=torch.float32)
-    check(_lib.load().nerfhip_mesh_shade(ptr(rays), n, ptr(tri), ptr(b1), ptr(b2), ptr(vertices), vertices.shape[0], ptr(triangles),
-                                         triangles.shape[0], ptr(colors), ambient, background, ptr(rgb), stream_ptr()), "nerfhip_mesh_shade")
-    return rgb
+    return _mesh_shade(_DeviceArrays, rays, tri, b1, b2, vertices, triangles, colors, ambient, background)
 
 
 def mesh_shade_host(rays, tri, b1, b2, vertices, triangles, colors=None, ambient=1.0, background=0.0):
     """nerfhip_mesh_shade_host (host, no GPU): numpy in, numpy rgb (n, 3) out."""
-    import numpy as np
-    rays = _rays_host("mesh_shade_host", rays)
-    tri, b1, b2 = _np16(tri, np.int32), _np16(b1, np.float32), _np16(b2, np.float32)
-    vertices, triangles = _mesh_arrays_host("mesh_shade_host", vertices, triangles)
-    n = rays.shape[0]
-    if not tri.shape == b1.shape == b2.shape == (n,):
-        raise ValueError("mesh_shade_host: tri, b1 and b2 must have one entry per ray")
-    if colors is not None:
-        colors = _np16(colors, np.uint8)
-        if colors.shape != vertices.shape:
-            raise ValueError("mesh_shade_host: colours must be (V, 3), got %s" % (colors.shape,))
-    ambient, background = _shade_scalars("mesh_shade_host", ambient, background)
-    rgb = _np_out((n, 3), np.float32)
-    check(_lib.load().nerfhip_mesh_shade_host(rays.ctypes.data, n, tri.ctypes.data, b1.ctypes.data, b2.ctypes.data, vertices.ctypes.data,
-                                              vertices.shape[0], triangles.ctypes.data, triangles.shape[0],
-                                              None if colors is None else colors.ctypes.data, ambient, background, rgb.ctypes.data),
-          "nerfhip_mesh_shade_host")
-    return rgb
+    return _mesh_shade(_HostArrays, rays, tri, b1, b2, vertices, triangles, colors, ambient, background)
 
 
-def _mixed_scalars(what, mode, tau, background):
+def _mixed_compose(B, mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background):
+    what = "mixed_compose" + B.suffix
     if mode not in MIXED_MODES:
         raise ValueError("%s: mode must be 'ztest' or 'clip', got %r" % (what, mode))
     tau = float(tau)
     if not tau > 0.0:
         raise ValueError("%s: tau must be > 0, got %r" % (what, tau))
-    return MIXED_MODES[mode], tau, float(background)
+    rgb_n, rgb_m = B.array(what, "rgb_n", rgb_n, "float32", (3,)), B.array(what, "rgb_m", rgb_m, "float32", (3,))
+    depth_n, opacity_n = B.array(what, "depth_n", depth_n, "float32", ()), B.array(what, "opacity_n", opacity_n, "float32", ())
+    tri, t = B.array(what, "tri", tri, "int32", ()), B.array(what, "t", t, "float32", ())
+    n = rgb_n.shape[0]
+    if not rgb_m.shape[0] == depth_n.shape[0] == opacity_n.shape[0] == tri.shape[0] == t.shape[0] == n:
+        raise ValueError("%s: every input must have one row per ray" % what)
+    B.same_device(what, rgb_n, depth_n, opacity_n, tri, t, rgb_m)
+    rgb, depth, opacity, mask = (B.empty(rgb_n, shape, dtype)
+                                 for shape, dtype in (((n, 3), "float32"), (n, "float32"), (n, "float32"), (n, "uint8")))
+    B.call("nerfhip_mixed_compose", MIXED_MODES[mode], n, B.ptr(rgb_n), B.ptr(depth_n), B.ptr(opacity_n), B.ptr(tri), B.ptr(t),
+           B.ptr(rgb_m), tau, float(background), B.ptr(rgb), B.ptr(depth), B.ptr(opacity), B.ptr(mask))
+    return rgb, depth, opacity, mask
 
 
 @device_guard
@@ -2101,37 +2083,9 @@ def mixed_compose(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, backg
     `mesh_shade`) -> (rgb, depth, opacity, mask (n,) uint8).  'ztest': the mesh wins where it is hit and t < depth_n / opacity_n
     (+inf where opacity_n < tau).  'clip': the render was made with far = min(far, t) on the hit rays and no background; the mesh,
     or `background` on a miss, fills the transmittance it left (include/nerfhip.h)."""
-    code, tau, background = _mixed_scalars("mixed_compose", mode, tau, background)
-    rgb_n = _require_dev("mixed_compose", "rgb_n", rgb_n, torch.float32, (3,))
-    rgb_m = _require_dev("mixed_compose", "rgb_m", rgb_m, torch.float32, (3,))
-    depth_n = _require_dev("mixed_compose", "depth_n", depth_n, torch.float32, ())
-    opacity_n = _require_dev("mixed_compose", "opacity_n", opacity_n, torch.float32, ())
-    tri = _require_dev("mixed_compose", "tri", tri, torch.int32, ())
-    t = _require_dev("mixed_compose", "t", t, torch.float32, ())
-    n = rgb_n.shape[0]
-    if not rgb_m.shape[0] == depth_n.shape[0] == opacity_n.shape[0] == tri.shape[0] == t.shape[0] == n:
-        raise ValueError("mixed_compose: every input must have one row per ray")
-    _same_device("mixed_compose", rgb_n, depth_n, opacity_n, tri, t, rgb_m)
-    dev = rgb_n.device
-    rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
-    depth, opacity = torch.empty(n, device=dev, dtype=torch.float32), torch.empty(n, device=dev, dtype=torch.float32)
-    mask = torch.empty(n, device=dev, dtype=torch.uint8)
-    check(_lib.load().nerfhip_mixed_compose(code, n, ptr(rgb_n), ptr(depth_n), ptr(opacity_n), ptr(tri), ptr(t), ptr(rgb_m), tau, background,
-                                            ptr(rgb), ptr(depth), ptr(opacity), ptr(mask), stream_ptr()), "nerfhip_mixed_compose")
-    return rgb, depth, opacity, mask
+    return _mixed_compose(_DeviceArrays, mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background)
 
 
 def mixed_compose_host(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, background=0.0):
     """nerfhip_mixed_compose_host (host, no GPU): numpy in, numpy (rgb, depth, opacity, mask) out."""
-    import numpy as np
-    code, tau, background = _mixed_scalars("mixed_compose_host", mode, tau, background)
-    rgb_n, rgb_m = _np16(rgb_n, np.float32), _np16(rgb_m, np.float32)
-    depth_n, opacity_n, t, tri = _np16(depth_n, np.float32), _np16(opacity_n, np.float32), _np16(t, np.float32), _np16(tri, np.int32)
-    n = depth_n.shape[0]
-    if not (rgb_n.shape == rgb_m.shape == (n, 3) and depth_n.shape == opacity_n.shape == t.shape == tri.shape == (n,)):
-        raise ValueError("mixed_compose_host: every input must have one row per ray")
-    rgb, depth, opacity, mask = _np_out((n, 3), np.float32), _np_out(n, np.float32), _np_out(n, np.float32), _np_out(n, np.uint8)
-    check(_lib.load().nerfhip_mixed_compose_host(code, n, rgb_n.ctypes.data, depth_n.ctypes.data, opacity_n.ctypes.data, tri.ctypes.data,
-                                                 t.ctypes.data, rgb_m.ctypes.data, tau, background, rgb.ctypes.data, depth.ctypes.data,
-                                                 opacity.ctypes.data, mask.ctypes.data), "nerfhip_mixed_compose_host")
-    return rgb, depth, opacity, mask
+    return _mixed_compose(_HostArrays, mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background)

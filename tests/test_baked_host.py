@@ -255,3 +255,39 @@ def test_python_wrappers_check_sizes(lib):
         baked.BakedVolume(torch.zeros(ops.baked_bytes(9), dtype=torch.uint8), 9, R.RANGES)
     with pytest.raises(NerfHipError):
         ops.baked_render(torch.zeros(3, 8), torch.zeros(ops.baked_bytes(9), dtype=torch.uint8), None, 9, R.RANGES, 0.25)
+
+
+# --------------------------------------------------------------------------------------------------- optional outputs left out
+def aligned(a):
+    """a copy of `a` whose data is 16-byte aligned, as the entry points want rays and the volume"""
+    buf = np.empty(a.nbytes + 16, np.uint8)
+    off = (-buf.ctypes.data) & 15
+    out = buf[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def null_output_case(n):
+    """(rays, bricked volume, bitfield words, the C call's scalars after `words`) of the N = 9 random lattice — two bricks per
+    axis — and n of its fixture's rays spread over all kinds, the zero-direction row included"""
+    N = 9
+    rays = R.rays(N)
+    rays = aligned(rays[np.linspace(0, len(rays) - 1, n).astype(int)])
+    _, data, bits = bricked("random", N)
+    rg = (ctypes.c_float * 6)(*[v for r in R.RANGES for v in r])
+    return rays, aligned(data), bits, (N, rg, R.cell_of(N), 0.5, 0.0, 1)
+
+
+def test_null_optional_outputs_of_render(lib):
+    """rgb, depth and opacity may each be null: the two that are supplied keep the bits of the full call."""
+    from nerf_pl_amd import ops
+    rays, data, bits, scalars = null_output_case(65)
+    n = len(rays)
+    full = ops.baked_render_host(rays, data, bits, 9, R.RANGES, R.cell_of(9), 0.5, 0.0, True)
+    assert full[2].max() > 0.05 and (full[2] == 0).any()
+    for skip in range(3):
+        out = [np.full((n, 3), np.nan, np.float32), np.full(n, np.nan, np.float32), np.full(n, np.nan, np.float32)]
+        ptrs = [None if k == skip else out[k].ctypes.data for k in range(3)]
+        assert lib.nerfhip_baked_render_host(rays.ctypes.data, n, data.ctypes.data, bits.ctypes.data, *scalars, *ptrs) == 0
+        keep = [k for k in range(3) if k != skip]
+        assert same_bits([out[k] for k in keep], [full[k] for k in keep]), skip

@@ -185,3 +185,29 @@ def test_from_model_is_export_then_records(dev):
     assert a.N == b.N == 9 and a.cell == b.cell == pytest.approx(2.0 / 9) and a.ranges == b.ranges
     assert torch.equal(a.data, b.data) and torch.equal(a.bits, b.bits)
     assert np.array_equal(a.to_dense().cpu().numpy(), volume.read_vol(rec.cpu().numpy().view(np.uint32).astype("<u4").tobytes(), 9))
+
+
+# --------------------------------------------------------------------------------------------------- optional outputs left out
+def test_null_optional_outputs_on_the_device(dev):
+    """nerfhip_baked_render with rgb, depth and opacity null in turn, on 257 rays (one full block and one ray in a second) through
+    the N = 9 lattice: the two that are supplied keep the bits of the full call, and nothing is written past row n of either."""
+    import test_baked_host as H
+    from nerf_pl_amd import _lib, ops
+    lib = _lib.load()
+    n, pad, pattern = 257, 64, -1515870811                  # 0xa5a5a5a5
+    rays, data, bits, scalars = H.null_output_case(n)
+    rays, data, bits = (torch.from_numpy(a).to(dev) for a in (rays, data, bits))
+    full = ops.baked_render(rays, data, bits, 9, R.RANGES, R.cell_of(9), 0.5, 0.0, True)
+    assert float(full[2].max()) > 0.05 and bool((full[2] == 0).any())
+    with torch.cuda.device(dev):
+        for skip in range(3):
+            out = [torch.full((n + pad,) + tail, pattern, device=dev, dtype=torch.int32).view(torch.float32) for tail in ((3,), (), ())]
+            ptrs = [None if k == skip else _lib.ptr(out[k]) for k in range(3)]
+            _lib.check(lib.nerfhip_baked_render(_lib.ptr(rays), n, _lib.ptr(data), _lib.ptr(bits), *scalars, *ptrs, _lib.stream_ptr()),
+                       "nerfhip_baked_render")
+            for k in range(3):
+                assert bool((out[k][n:].view(torch.int32) == pattern).all()), (skip, k)
+                if k == skip:
+                    assert bool((out[k].view(torch.int32) == pattern).all()), skip
+                else:
+                    assert torch.equal(out[k][:n].view(torch.int32), full[k].view(torch.int32)), (skip, k)

@@ -265,3 +265,43 @@ def test_cpu_tensors_raise(dev):
     from nerf_pl_amd.meshcast import MeshRenderer
     with pytest.raises(NerfHipError):
         MeshRenderer(b, True)(torch.from_numpy(R.pinhole()))
+
+
+# --------------------------------------------------------------------------------------------------- optional outputs left out
+def test_null_optional_outputs_on_the_device(dev):
+    """nerfhip_mesh_cast with t, b1 and b2 null and nerfhip_mixed_compose without a mask, on 257 rays (one full block and one ray
+    in a second): what is supplied keeps the bits of the full call, and nothing is written past row n of any output."""
+    from nerf_pl_amd import _lib, ops
+    lib = _lib.load()
+    n, pad = 257, 64
+    _, _, b = bvh(dev, "soup5")
+    assert b.tris.shape == (5, 12) and b.boxes.shape == (3, 6)
+    rays = torch.from_numpy(H.null_output_rays(n)).to(dev)
+    full = ops.mesh_cast(rays, b.tris, b.boxes)
+    assert bool((full[0] >= 0).any()) and bool((full[0] < 0).any())
+
+    pattern = -1515870811                                   # 0xa5a5a5a5
+
+    def fresh(specs):
+        """outputs of n + pad rows filled with the pattern"""
+        return [torch.full((n + pad,) + tail, pattern, device=dev, dtype=torch.int32).view(dtype) for tail, dtype in specs]
+
+    def untouched(outs):
+        return all(bool((o[n:].view(torch.int32) == pattern).all()) for o in outs)
+
+    with torch.cuda.device(dev):
+        for nulls in H.CAST_NULLS:
+            out = fresh([((), torch.int32), ((), torch.float32), ((), torch.float32), ((), torch.float32)])
+            args = [None if k in nulls else out[k] for k in range(4)]
+            _lib.check(lib.nerfhip_mesh_cast(_lib.ptr(rays), n, _lib.ptr(b.tris), _lib.ptr(b.boxes), 5, *[_lib.ptr(a) for a in args],
+                                             _lib.stream_ptr()), "nerfhip_mesh_cast")
+            assert same_bits(cpu([a[:n] for a in args if a is not None]), cpu([full[k] for k in range(4) if k not in nulls])), nulls
+            assert untouched(out), nulls
+        inputs = [torch.from_numpy(a).to(dev) for a in H.compose_inputs(n)]
+        for mode in ("ztest", "clip"):
+            want = ops.mixed_compose(mode, *inputs, tau=0.5, background=1.0)
+            out = fresh([((3,), torch.float32), ((), torch.float32), ((), torch.float32)])
+            _lib.check(lib.nerfhip_mixed_compose(ops.MIXED_MODES[mode], n, *[_lib.ptr(a) for a in inputs], 0.5, 1.0,
+                                                 *[_lib.ptr(a) for a in out], None, _lib.stream_ptr()), "nerfhip_mixed_compose")
+            assert same_bits(cpu([a[:n] for a in out]), cpu(want[:3])), mode
+            assert untouched(out), mode

@@ -344,3 +344,54 @@ def test_python_layer_refuses_cpu_tensors_and_bad_shapes():
         MixedRenderer(White(), None, True, mode="clip")
     with pytest.raises(ValueError):
         MixedRenderer(White(), None, True, mode="blend")
+
+
+# --------------------------------------------------------------------------------------------------- optional outputs left out
+def aligned(a):
+    """a copy of `a` whose data is 16-byte aligned, as the entry points want rays and triangles"""
+    buf = np.empty(a.nbytes + 16, np.uint8)
+    off = (-buf.ctypes.data) & 15
+    out = buf[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def null_output_rays(n):
+    """n rays from the camera towards seeded points within 0.4 of the centres of soup5's triangles (about half of them hit), the
+    last one a NaN row"""
+    v, t = R.soup(5)
+    rng = np.random.default_rng(29)
+    target = v[t].mean(1)[np.arange(n) % 5] + rng.uniform(-0.4, 0.4, (n, 3))
+    rays = R._rows(np.array(R.CAMERA)[None], target - np.array(R.CAMERA), 0.0, 100.0)
+    rays[-1, 4] = np.nan
+    return aligned(rays)
+
+
+CAST_NULLS = ((1,), (2,), (3,), (1, 2, 3))                 # of (tri, t, b1, b2): each optional output alone, then all three
+
+
+def test_null_optional_outputs_of_cast_and_compose(lib):
+    """t, b1 and b2 of the cast and the mask of compose may be null: what is supplied keeps the bits of the full call.  soup5 is
+    the smallest hierarchy with an inner node: two leaves and a root."""
+    from nerf_pl_amd import ops
+    _, _, (tris, boxes, _, _) = built("soup5")
+    assert tris.shape == (5, 12) and boxes.shape == (3, 6)
+    rays = null_output_rays(65)
+    n = len(rays)
+    full = ops.mesh_cast_host(rays, tris, boxes)
+    assert (full[0] >= 0).any() and (full[0] < 0).any() and full[0][-1] == -1
+
+    def p(a):
+        return None if a is None else a.ctypes.data
+    for nulls in CAST_NULLS:
+        out = [np.full(n, -7, np.int32)] + [np.full(n, np.nan, np.float32) for _ in range(3)]
+        args = [None if k in nulls else out[k] for k in range(4)]
+        assert lib.nerfhip_mesh_cast_host(p(rays), n, p(tris), p(boxes), 5, 0, *[p(a) for a in args]) == 0
+        assert same_bits([a for a in args if a is not None], [full[k] for k in range(4) if k not in nulls]), nulls
+    inputs = compose_inputs(n)
+    for mode in ("ztest", "clip"):
+        want = ops.mixed_compose_host(mode, *inputs, tau=0.5, background=1.0)
+        assert want[3].any() and not want[3].all()
+        out = [np.full((n, 3), np.nan, np.float32), np.full(n, np.nan, np.float32), np.full(n, np.nan, np.float32)]
+        assert lib.nerfhip_mixed_compose_host(ops.MIXED_MODES[mode], n, *[p(a) for a in inputs], 0.5, 1.0, *[p(a) for a in out], None) == 0
+        assert same_bits(out, want[:3]), mode

@@ -8,6 +8,7 @@
 // exactly nerfhip_baked_bytes(N) bytes, forms the cell-brick bitfield by its rule into exactly ceil(MB^3 / 32) words, and marches
 // rays of every kind (through the box, beside it, inside it, axis-parallel with zeros of both signs, non-finite) at step 1/16, 0.5
 // and 8 with the bitfield and without it: the two must agree bit for bit, and a read outside a block is the sanitizer's to report.
+// A last pass hands null to rgb, depth and opacity in turn: the outputs that are supplied must keep the bits of the full call.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -99,6 +100,21 @@ int main() {
                         ++failures;
                     }
                 }
+        // every optional output null in turn: the outputs that are supplied keep the bits of the full call (out[1], the last one)
+        const size_t size[3] = {sizeof(float) * 3 * n, sizeof(float) * n, sizeof(float) * n};
+        for (int skip = 0; skip < 3; ++skip) {
+            float* o[3];
+            for (int k = 0; k < 3; ++k) {
+                o[k] = k == skip ? nullptr : out[0][k];
+                if (o[k]) memset(o[k], 0xa5, size[k]);
+            }
+            const int e = nerfhip_baked_render_host(rays, n, data, words, N, ranges, cell, 8.0f, 0.01f, 1, o[0], o[1], o[2]);
+            for (int k = 0; k < 3; ++k)
+                if (e || (o[k] && memcmp(o[k], out[1][k], size[k]))) {
+                    printf("N %d: output %d null: error %d or output %d differs from the full call\n", N, skip, e, k);
+                    ++failures;
+                }
+        }
         double sum = 0;
         for (int i = 0; i < n; ++i) sum += out[1][2][i];
         printf("N %2d: %d rays, mean opacity %.4f\n", N, n, sum / n);

@@ -10,6 +10,8 @@
 // * 6 floats — and casts rays of every kind (through the soup, beside it, from inside, axis-parallel with zeros of both signs,
 // non-finite, zero direction, short windows) with the hierarchy and without it: the two must agree bit for bit, no bad triangle
 // may be returned, and a read or write outside a block is the sanitizer's to report.  The hits are then shaded and composed.
+// The cast runs again with t, b1 and b2 null (each alone and all three) and the compose with a null mask: the outputs that are
+// supplied must keep the bits of the full call.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -119,6 +121,22 @@ int main() {
             printf("T %lld: the hierarchy changed the result\n", (long long)T);
             ++failures;
         }
+        // t, b1 and b2 null, each alone and all three: what is supplied keeps the bits of the full call
+        for (int skip = 0; skip < 4; ++skip) {
+            float* o[3];
+            for (int k = 0; k < 3; ++k) {
+                o[k] = (k == skip || skip == 3) ? nullptr : out[1][k];
+                if (o[k]) memset(o[k], 0xa5, sizeof(float) * n);
+            }
+            if (n) memset(tri[1], 0xa5, sizeof(int32_t) * n);
+            e = nerfhip_mesh_cast_host(rays, n, tris, boxes, T, 0, tri[1], o[0], o[1], o[2]);
+            bool kept = !e && !memcmp(tri[1], tri[0], sizeof(int32_t) * n);
+            for (int k = 0; k < 3; ++k) kept = kept && (!o[k] || !memcmp(o[k], out[0][k], sizeof(float) * n));
+            if (!kept) {
+                printf("T %lld: cast with null outputs (%d): error %d or a supplied output differs\n", (long long)T, skip, e);
+                ++failures;
+            }
+        }
         int hits = 0;
         for (int i = 0; i < n; ++i) {
             const int32_t h = tri[0][i];
@@ -154,6 +172,16 @@ int main() {
                 printf("T %lld pass %d: shade / compose error %d\n", (long long)T, pass, e);
                 ++failures;
             }
+            // the mask null: rgb, depth and opacity keep the bits of the full call
+            float* again[3] = {block<float>((size_t)n * 3), block<float>(n), block<float>(n)};
+            e = nerfhip_mixed_compose_host(pass, n, rgb_n, depth_n, opacity_n, tri[0], out[0][0], rgb_m, 0.5f, (float)pass, again[0], again[1],
+                                           again[2], nullptr);
+            if (e || memcmp(again[0], rgb, sizeof(float) * 3 * n) || memcmp(again[1], depth, sizeof(float) * n) ||
+                memcmp(again[2], opacity, sizeof(float) * n)) {
+                printf("T %lld pass %d: compose without a mask: error %d or an output differs\n", (long long)T, pass, e);
+                ++failures;
+            }
+            for (float* p : again) free(p);
         }
         printf("T %3lld: %zu boxes, %lld bad, %d of %d rays hit\n", (long long)T, nodes, (long long)n_bad, hits, n);
         for (int s = 0; s < 2; ++s) {
