@@ -1002,6 +1002,102 @@ int nerfhip_mixed_compose_host(int mode, int64_t n, const float* rgb_n, const fl
                                const int32_t* tri, const float* t, const float* rgb_m, float tau, float background, float* rgb,
                                float* depth, float* opacity, uint8_t* mask_or_null);
 
+/* ---- mesh decimation: grid vertex clustering with mean or quadric placement  (no counterpart in the reference, whose answer to a
+ *      9.4 M triangle mesh is a coarser sigma grid) ----------------------------------------------------------------
+ * Opt-in and beside everything else.  csrc/decimate_core.h states every routine exactly, and every entry point has a _host twin
+ * (a HOST function: host pointers, no GPU, the same routine in a loop, the same bits).  Nothing is allocated, nothing
+ * synchronises, launches go to the caller's stream; the caller sorts between the calls (ops._mesh_decimate: torch.sort).
+ *
+ * Inputs: vertices (V,3) fp32, triangles (T,3) int32, optional colors (V,3) uint8, cell > 0 finite fp32, optional origin.
+ * 0 <= V, T <= 2^28.  The result (a contract, whatever computes it):
+ *  1 bad input.  A vertex with a non-finite coordinate belongs to no cluster.  A triangle with an index outside [0, V) or such
+ *    a vertex is BAD: dropped and counted (mesh_bvh's rule).
+ *  2 cells.  lo = the per-axis minimum over the finite vertices, or the origin (no finite vertex may lie below it).
+ *    q_a = floorf((v_a - lo_a) / cell) in fp32, subtraction and IEEE division separately rounded; R_a = max q_a + 1;
+ *    cell number c = (q0 R1 + q1) R2 + q2; R0 R1 R2 < 2^31.
+ *  3 clusters.  The keys c << 32 | vertex (c = 2^31 - 1 for a vertex of no cluster; distinct, so the sort decides nothing) are
+ *    sorted; the non-empty cells, in ascending c, are the clusters 0 .. C - 1; cluster_of[v] is the vertex's cluster or -1.
+ *  4 mean.  m = the fp64 sum of the members in ascending vertex number over their count n.  Colours: per channel the integer
+ *    sum s, output (2 s + n) / (2 n) in integers.
+ *  5 quadric.  Every good triangle t, also one that collapses in 6, has the entries e = 3 t + k, k = 0..2, each in the cluster
+ *    of corner k; the keys cluster << 32 | e are sorted.  Per cluster, in ascending e, in fp64 on the fp32 coordinates:
+ *    n = (p1 - p0) x (p2 - p0), d = -n . (p0 - m), A += n n^T, b += d n.  lambda = eps (A00 + A11 + A22); x = 0 if that trace
+ *    is 0 or not finite, else the solution of (A + lambda I) x = -b (cofactors), 0 if not finite.  position = clamp(m + x,
+ *    blo, bhi) per axis, blo_a = (double)lo_a + q_a (double)cell, bhi = blo + (double)cell.  Mean placement is x = 0 without
+ *    the clamp.  Either is rounded to fp32 once.
+ *  6 triangles.  Good triangles are mapped through cluster_of; one with two equal clusters is COLLAPSED; of those equal after
+ *    rotating the smallest cluster to the front (the same orientation) the one with the lowest number stays, the others are
+ *    DUPLICATES.  Survivors keep their order and their corner order.
+ *  7 vertices.  A cluster no survivor names is UNREFERENCED and removed; the others keep their order; triangles and cluster_of
+ *    are renumbered (-1 for a vertex of a removed cluster).
+ *
+ * The passes (every array on the device, or on the host for a _host twin; 4-byte aligned, int64 and double arrays 8-byte):
+ * bounds: state, 8 int32 — [0] the non-finite vertices, [1] 0, [2..4] / [5..7] lo / hi of the finite ones as order-preserving
+ *   integers (csrc/mesh_core.h mesh_ordered; +inf / -inf when there is none).
+ * keys: lo_host (3 floats), cell and res_host (R, 3 int32) on the HOST -> keys (V) int64.
+ * clusters: sorted_keys (V) ascending -> cluster_of (V) int32; seg_start (>= C + 1) int32, cluster i being the sorted positions
+ *   [seg_start[i], seg_start[i + 1]); totals[0] = C (int64, on the device).  blk (ceil(V / 256)) int32 and off (the same count)
+ *   int64 are scratch.
+ * entries: -> keys (3 T) int64, cluster 2^31 - 1 for the corners of a bad triangle.
+ * place: placement 0 mean, 1 quadric (reads sorted_entries (3 T), else unused); 0 < eps <= 1 -> mean (C,3) fp64, positions
+ *   (C,3) fp32, colors_out (C,3) uint8 (null with colors).
+ * tri_keys: -> flags (T) uint8: 0 candidate, 1 bad, 2 collapsed; key_hi = a << 28 | b, key_lo = c << 28 | t of the rotated
+ *   clusters (a, b, c); key_hi = 2^63 - 1 and key_lo = t for a triangle that is no candidate.
+ * duplicates: the two arrays in ascending (key_hi, key_lo) order -> flags[t] = 3 for every duplicate.
+ * mark: -> ref (C) uint8, 1 for a cluster a survivor names; totals (5 int64, on the device) = T', V', bad, collapsed,
+ *   duplicate; blk_t / off_t (ceil(T / 256)) and blk_c / off_c (ceil(C / 256)): block totals (int32) and offsets (int64),
+ *   which compact reads.
+ * compact: -> vnew (C) int32, out_vertices (V',3), out_triangles (T',3), out_colors (V',3) or null, out_cluster_of (V).
+ *
+ * NERFHIP_E_BADARG before anything is launched or dereferenced: a count out of range, C > V, a null array that a non-zero
+ * count would read or write, cell <= 0 or not finite, a non-finite lo, an R < 1 or R0 R1 R2 >= 2^31, an unknown placement,
+ * colours in without colours out or the reverse.  NERFHIP_E_ALIGN as stated above.  A zero count is success.                    */
+int nerfhip_mesh_decimate_bounds(const float* vertices, int64_t V, int32_t* state, nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_bounds_host(const float* vertices, int64_t V, int32_t* state);
+int nerfhip_mesh_decimate_keys(const float* vertices, int64_t V, const float* lo_host, float cell, const int32_t* res_host,
+                               int64_t* keys, nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_keys_host(const float* vertices, int64_t V, const float* lo_host, float cell, const int32_t* res_host,
+                                    int64_t* keys);
+int nerfhip_mesh_decimate_clusters(const int64_t* sorted_keys, int64_t V, int32_t* blk, int64_t* off, int32_t* cluster_of,
+                                   int32_t* seg_start, int64_t* totals, nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_clusters_host(const int64_t* sorted_keys, int64_t V, int32_t* blk, int64_t* off, int32_t* cluster_of,
+                                        int32_t* seg_start, int64_t* totals);
+int nerfhip_mesh_decimate_entries(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of, int64_t* keys,
+                                  nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_entries_host(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of, int64_t* keys);
+int nerfhip_mesh_decimate_place(const float* vertices, int64_t V, const uint8_t* colors_or_null, const int32_t* triangles,
+                                int64_t T, const int64_t* sorted_keys, const int32_t* seg_start, int64_t C,
+                                const int64_t* sorted_entries, const float* lo_host, float cell, const int32_t* res_host,
+                                double eps, int placement, double* mean, float* positions, uint8_t* colors_out_or_null,
+                                nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_place_host(const float* vertices, int64_t V, const uint8_t* colors_or_null, const int32_t* triangles,
+                                     int64_t T, const int64_t* sorted_keys, const int32_t* seg_start, int64_t C,
+                                     const int64_t* sorted_entries, const float* lo_host, float cell, const int32_t* res_host,
+                                     double eps, int placement, double* mean, float* positions, uint8_t* colors_out_or_null);
+int nerfhip_mesh_decimate_tri_keys(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of, uint8_t* flags,
+                                   int64_t* key_hi, int64_t* key_lo, nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_tri_keys_host(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of, uint8_t* flags,
+                                        int64_t* key_hi, int64_t* key_lo);
+int nerfhip_mesh_decimate_duplicates(const int64_t* sorted_hi, const int64_t* sorted_lo, int64_t T, uint8_t* flags,
+                                     nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_duplicates_host(const int64_t* sorted_hi, const int64_t* sorted_lo, int64_t T, uint8_t* flags);
+int nerfhip_mesh_decimate_mark(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of, const uint8_t* flags,
+                               int64_t C, uint8_t* ref, int32_t* blk_t, int64_t* off_t, int32_t* blk_c, int64_t* off_c,
+                               int64_t* totals, nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_mark_host(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of,
+                                    const uint8_t* flags, int64_t C, uint8_t* ref, int32_t* blk_t, int64_t* off_t, int32_t* blk_c,
+                                    int64_t* off_c, int64_t* totals);
+int nerfhip_mesh_decimate_compact(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of, const uint8_t* flags,
+                                  int64_t C, const uint8_t* ref, const int64_t* off_t, const int64_t* off_c,
+                                  const float* positions, const uint8_t* colors_or_null, int32_t* vnew, float* out_vertices,
+                                  int32_t* out_triangles, uint8_t* out_colors_or_null, int32_t* out_cluster_of,
+                                  nerfhip_stream_t stream);
+int nerfhip_mesh_decimate_compact_host(const int32_t* triangles, int64_t T, int64_t V, const int32_t* cluster_of,
+                                       const uint8_t* flags, int64_t C, const uint8_t* ref, const int64_t* off_t,
+                                       const int64_t* off_c, const float* positions, const uint8_t* colors_or_null, int32_t* vnew,
+                                       float* out_vertices, int32_t* out_triangles, uint8_t* out_colors_or_null,
+                                       int32_t* out_cluster_of);
+
 #ifdef __cplusplus
 }
 #endif

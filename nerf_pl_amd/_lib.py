@@ -194,6 +194,24 @@ SIGNATURES = {
                                    _c_void_p, _c_void_p, _c_void_p],
 }
 
+# mesh decimation (csrc/decimate.hip): a device entry point is its _host twin's arguments plus the stream
+_DECIMATE = {
+    "bounds": [_c_void_p, _i64, _c_void_p],
+    "keys": [_c_void_p, _i64, _c_void_p, _f32, _c_void_p, _c_void_p],
+    "clusters": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "entries": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p],
+    "place": [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _f32, _c_void_p, _f64, _int,
+              _c_void_p, _c_void_p, _c_void_p],
+    "tri_keys": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "duplicates": [_c_void_p, _c_void_p, _i64, _c_void_p],
+    "mark": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "compact": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+}
+for _name, _args in _DECIMATE.items():
+    SIGNATURES["nerfhip_mesh_decimate_" + _name] = _args + [_c_void_p]
+    SIGNATURES["nerfhip_mesh_decimate_%s_host" % _name] = list(_args)
+
 
 class AdamFused(ctypes.Structure):
     """include/nerfhip.h: nerfhip_adam_fused"""

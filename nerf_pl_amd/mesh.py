@@ -204,16 +204,22 @@ def read_ply(path):
 @torch.no_grad()
 def extract_color_mesh(nerf_fine, embeddings, N_grid, x_range, y_range, z_range, sigma_threshold, poses=None, images=None,
                        focal=None, near=None, far=None, occ_threshold=0.2, N_samples=64, white_back=False, chunk=32 * 1024,
-                       use_vertex_normal=False, nerf_coarse=None, N_importance=64, near_t=1.0, coords="reference"):
+                       use_vertex_normal=False, nerf_coarse=None, N_importance=64, near_t=1.0, coords="reference",
+                       decimate_cell=None, decimate_placement="mean"):
     """extract_color_mesh.py end to end: sigma_grid -> marching_cubes -> world_coords -> keep_largest_cluster ->
     fuse_vertex_colors.  Returns numpy (vertices (V,3) float32 world, triangles (T,3) int32, colors (V,3) uint8); colors is None
-    when neither poses/images (default mode) nor use_vertex_normal is given.  write_ply(path, *result) writes the reference's file."""
+    when neither poses/images (default mode) nor use_vertex_normal is given.  write_ply(path, *result) writes the reference's file.
+    decimate_cell (world units; None: the reference's mesh) clusters the vertices of the largest cluster into cells of that edge
+    (decimate.py) before the colour fusion, which then renders one ray per remaining vertex and view."""
     sigma = sigma_grid(nerf_fine, N_grid, x_range, y_range, z_range, embedding_xyz=embeddings[0])
     v_idx, tris = marching_cubes(sigma, sigma_threshold)
     dev = sigma.device
     v_world = torch.from_numpy(world_coords(v_idx, N_grid, x_range, y_range, z_range, coords)).to(dev)
     if tris.shape[0]:
         v_world, tris = keep_largest_cluster(v_world, tris)
+    if decimate_cell is not None and tris.shape[0]:
+        from .decimate import decimate
+        v_world, tris, _ = decimate(v_world, tris, None, cell=decimate_cell, placement=decimate_placement)
     colors = None
     if tris.shape[0] and (use_vertex_normal or poses is not None):
         colors = fuse_vertex_colors(v_world, poses, images, focal, near, nerf_fine, embeddings, occ_threshold, N_samples, white_back,

@@ -62,6 +62,11 @@ class MeshBVH:
         """Bad triangles of the mesh (one host read)."""
         return int(self._n_bad.item())
 
+    def decimated(self, cell, placement="mean"):
+        """A new MeshBVH of this mesh clustered into cells of edge `cell` (decimate.py), colours included."""
+        from .decimate import decimate
+        return MeshBVH(*decimate(self.vertices, self.triangles, self.colors, cell=cell, placement=placement))
+
     def cast(self, rays):
         """rays (n, 8) on the device -> (tri (n,) int32, -1 for a miss; t (n,); b1 (n,); b2 (n,)): ops.mesh_cast."""
         return ops.mesh_cast(rays, self.tris, self.boxes)

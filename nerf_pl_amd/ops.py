@@ -1651,6 +1651,20 @@ class _DeviceArrays:
         return torch.sort(keys)[0]
 
     @staticmethod
+    def sort_stable(keys):
+        """(the keys in ascending order, the position each came from); equal keys keep their order"""
+        return torch.sort(keys, stable=True)
+
+    @staticmethod
+    def take(a, index):
+        return a[index]
+
+    @staticmethod
+    def host(a):
+        """a small array read back to the host (synchronises)"""
+        return a.cpu().numpy()
+
+    @staticmethod
     def call(name, *args):
         check(getattr(_lib.load(), name)(*args, stream_ptr()), name)
 
@@ -1681,6 +1695,20 @@ class _HostArrays:
     def sort(keys):
         import numpy as np
         return _np16(np.sort(keys), keys.dtype)
+
+    @staticmethod
+    def sort_stable(keys):
+        import numpy as np
+        order = np.argsort(keys, kind="stable")
+        return _np16(keys[order], keys.dtype), order
+
+    @staticmethod
+    def take(a, index):
+        return _np16(a[index], a.dtype)
+
+    @staticmethod
+    def host(a):
+        return a
 
     @staticmethod
     def call(name, *args):
@@ -2089,3 +2117,121 @@ def mixed_compose(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, backg
 def mixed_compose_host(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, background=0.0):
     """nerfhip_mixed_compose_host (host, no GPU): numpy in, numpy (rgb, depth, opacity, mask) out."""
     return _mixed_compose(_HostArrays, mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background)
+
+
+# ---- mesh decimation (csrc/decimate.hip, DESIGN.md §22) -----------------------------------------------------------------------
+DECIMATE_MAX_ITEMS = 1 << 28
+DECIMATE_PLACEMENTS = {"mean": 0, "quadric": 1}
+DECIMATE_COUNTS = ("clusters", "bad", "collapsed", "duplicate", "unreferenced")
+
+
+def _mesh_decimate(B, vertices, triangles, colors, cell, placement, origin, eps):
+    import numpy as np
+    what = "mesh_decimate" + B.suffix
+    vertices, triangles = _mesh_arrays(B, what, vertices, triangles)
+    V, T = vertices.shape[0], triangles.shape[0]
+    if V > DECIMATE_MAX_ITEMS:
+        raise ValueError("%s: at most 2^28 vertices, got %d" % (what, V))
+    if colors is not None:
+        colors = B.array(what, "colors", colors, "uint8", (3,))
+        if colors.shape[0] != V:
+            raise ValueError("%s: %d colours for %d vertices" % (what, colors.shape[0], V))
+    B.same_device(what, vertices, triangles, colors)
+    if placement not in DECIMATE_PLACEMENTS:
+        raise ValueError("%s: placement must be 'mean' or 'quadric', got %r" % (what, placement))
+    cell32, eps = np.float32(cell), float(eps)
+    if not (np.isfinite(cell32) and cell32 > 0):
+        raise ValueError("%s: cell must be > 0 and finite as fp32, got %r" % (what, cell))
+    if not 0.0 < eps <= 1.0:
+        raise ValueError("%s: eps must be in (0, 1], got %r" % (what, eps))
+    if origin is not None:
+        origin = np.asarray(origin, np.float32).reshape(-1)
+        if origin.shape != (3,) or not np.isfinite(origin).all():
+            raise ValueError("%s: origin must be 3 finite floats, got %r" % (what, origin))
+
+    def result(n_v, n_t, cluster_of, counts, arrays=None):
+        out_v, out_t = B.empty(vertices, (max(n_v, 1), 3), "float32"), B.empty(vertices, (max(n_t, 1), 3), "int32")
+        out_c = None if colors is None else B.empty(vertices, (max(n_v, 1), 3), "uint8")
+        if arrays is not None:
+            arrays(out_v, out_t, out_c)
+        return out_v[:n_v], out_t[:n_t], None if out_c is None else out_c[:n_v], cluster_of, dict(zip(DECIMATE_COUNTS, counts))
+
+    def nothing(bad):
+        cluster_of = B.empty(vertices, V, "int32")
+        cluster_of[...] = -1
+        return result(0, 0, cluster_of, (0, bad, 0, 0, 0))
+
+    if V == 0 or T == 0:
+        return nothing(0)
+    state = B.empty(vertices, 8, "int32")
+    B.call("nerfhip_mesh_decimate_bounds", B.ptr(vertices), V, B.ptr(state))
+    words = np.ascontiguousarray(B.host(state), np.int32).view(np.uint32)
+    if int(words[0]) == V:                         # no finite vertex: every triangle is bad
+        return nothing(T)
+    bits = np.where(words[2:] >> 31, words[2:] & np.uint32(0x7fffffff), ~words[2:]).astype(np.uint32)      # mesh_core.h mesh_unordered
+    v_lo, v_hi = bits.view(np.float32)[:3], bits.view(np.float32)[3:]
+    lo = v_lo if origin is None else origin
+    if (v_lo < lo).any():
+        raise ValueError("%s: a vertex lies below the origin %s (the mesh starts at %s)" % (what, lo.tolist(), v_lo.tolist()))
+    with np.errstate(all="ignore"):
+        q_max = np.floor((v_hi - lo) / cell32)     # the kernel's fp32 operations: q is monotonic in v
+    if not np.isfinite(q_max).all() or (int(q_max[0]) + 1) * (int(q_max[1]) + 1) * (int(q_max[2]) + 1) >= 1 << 31:
+        raise ValueError("%s: cell too small for this mesh (2^31 cells or more)" % what)
+    lo_c, res_c = (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_int32 * 3)(*(int(q) + 1 for q in q_max))
+    grid = (lo_c, float(cell32), res_c)
+
+    def blocks(n):
+        return (n + 255) // 256
+
+    keys = B.empty(vertices, V, "int64")
+    B.call("nerfhip_mesh_decimate_keys", B.ptr(vertices), V, *grid, B.ptr(keys))
+    sorted_keys = B.sort(keys)
+    blk, off = B.empty(vertices, blocks(V), "int32"), B.empty(vertices, blocks(V), "int64")
+    cluster_of, seg_start, totals = B.empty(vertices, V, "int32"), B.empty(vertices, V + 1, "int32"), B.empty(vertices, 5, "int64")
+    B.call("nerfhip_mesh_decimate_clusters", B.ptr(sorted_keys), V, B.ptr(blk), B.ptr(off), B.ptr(cluster_of), B.ptr(seg_start),
+           B.ptr(totals))
+    C = int(B.host(totals)[0])
+    entries = None
+    if placement == "quadric":
+        entries = B.empty(vertices, 3 * T, "int64")
+        B.call("nerfhip_mesh_decimate_entries", B.ptr(triangles), T, V, B.ptr(cluster_of), B.ptr(entries))
+        entries = B.sort(entries)
+    mean, positions = B.empty(vertices, (C, 3), "float64"), B.empty(vertices, (C, 3), "float32")
+    cluster_colors = None if colors is None else B.empty(vertices, (C, 3), "uint8")
+    B.call("nerfhip_mesh_decimate_place", B.ptr(vertices), V, B.ptr(colors), B.ptr(triangles), T, B.ptr(sorted_keys), B.ptr(seg_start), C,
+           B.ptr(entries), *grid, eps, DECIMATE_PLACEMENTS[placement], B.ptr(mean), B.ptr(positions), B.ptr(cluster_colors))
+    # duplicates: the triangles in ascending (key_hi, key_lo) order, by a sort on the low half and a stable one on the high half
+    flags, key_hi, key_lo = B.empty(vertices, T, "uint8"), B.empty(vertices, T, "int64"), B.empty(vertices, T, "int64")
+    B.call("nerfhip_mesh_decimate_tri_keys", B.ptr(triangles), T, V, B.ptr(cluster_of), B.ptr(flags), B.ptr(key_hi), B.ptr(key_lo))
+    key_lo, order = B.sort_stable(key_lo)
+    key_hi, order = B.sort_stable(B.take(key_hi, order))
+    key_lo = B.take(key_lo, order)
+    B.call("nerfhip_mesh_decimate_duplicates", B.ptr(key_hi), B.ptr(key_lo), T, B.ptr(flags))
+    ref = B.empty(vertices, C, "uint8")
+    blk_t, off_t = B.empty(vertices, blocks(T), "int32"), B.empty(vertices, blocks(T), "int64")
+    blk_c, off_c = B.empty(vertices, blocks(C), "int32"), B.empty(vertices, blocks(C), "int64")
+    B.call("nerfhip_mesh_decimate_mark", B.ptr(triangles), T, V, B.ptr(cluster_of), B.ptr(flags), C, B.ptr(ref), B.ptr(blk_t), B.ptr(off_t),
+           B.ptr(blk_c), B.ptr(off_c), B.ptr(totals))
+    n_t, n_v, bad, collapsed, duplicate = (int(x) for x in B.host(totals))
+    vnew, out_cluster_of = B.empty(vertices, C, "int32"), B.empty(vertices, V, "int32")
+
+    def compact(out_v, out_t, out_c):
+        B.call("nerfhip_mesh_decimate_compact", B.ptr(triangles), T, V, B.ptr(cluster_of), B.ptr(flags), C, B.ptr(ref), B.ptr(off_t),
+               B.ptr(off_c), B.ptr(positions), B.ptr(cluster_colors), B.ptr(vnew), B.ptr(out_v), B.ptr(out_t), B.ptr(out_c),
+               B.ptr(out_cluster_of))
+    return result(n_v, n_t, out_cluster_of, (C, bad, collapsed, duplicate, C - n_v), compact)
+
+
+@device_guard
+def mesh_decimate(vertices, triangles, colors=None, cell=1.0, placement="mean", origin=None, eps=1e-3):
+    """nerfhip_mesh_decimate_*, with torch.sort between them: vertices (V, 3) fp32, triangles (T, 3) int32 and optional colors (V, 3)
+    uint8 on the device -> (vertices' (V', 3), triangles' (T', 3), colors' (V', 3) or None, cluster_of (V,) int32, counts: a dict of
+    clusters, bad, collapsed, duplicate, unreferenced) by the contract of include/nerfhip.h.  Reads back the bounds and the
+    counts.  ValueError for a cell that is not > 0 and finite, a grid of 2^31 cells or more, an origin above a vertex."""
+    return _mesh_decimate(_DeviceArrays, vertices, triangles, colors, cell, placement, origin, eps)
+
+
+def mesh_decimate_host(vertices, triangles, colors=None, cell=1.0, placement="mean", origin=None, eps=1e-3):
+    """The _host twins of `mesh_decimate` with numpy's sorts between them (host, no GPU): numpy in, numpy out, bit for bit what
+    the device computes."""
+    return _mesh_decimate(_HostArrays, vertices, triangles, colors, cell, placement, origin, eps)
