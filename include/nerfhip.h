@@ -1098,6 +1098,64 @@ int nerfhip_mesh_decimate_compact_host(const int32_t* triangles, int64_t T, int6
                                        float* out_vertices, int32_t* out_triangles, uint8_t* out_colors_or_null,
                                        int32_t* out_cluster_of);
 
+/* ---- texturing a triangle mesh: a per-triangle atlas, its sample points, the lookup  (README_Unity.md wants a small mesh with a
+ *      texture; no counterpart in the reference's code) -------------------------------------------------------------
+ * Opt-in and beside everything else.  csrc/texture_core.h states every routine exactly, and every entry point has a _host twin (a
+ * HOST function: host pointers, no GPU, the same routine in a loop, the same bits).  Nothing is allocated, nothing synchronises,
+ * launches go to the caller's stream.  The mesh is mesh_cast's: vertices (V,3) fp32, triangles (T,3) int32, 0 <= V < 2^31.
+ *
+ * The atlas (a public format).  res = R, 1 <= R <= 64, is the number of texel intervals along a patch leg; the block edge is
+ * B = R + 3.  Triangle t has n_tex = (R + 2)(R + 3) / 2 samples at the lattice points (i, j), i, j >= 0, i + j <= R + 1; sample
+ * (i, j) lies at the barycentric weights b1 = i / R (vertex 1), b2 = j / R (vertex 2), b0 = 1 - b1 - b2.  The diagonal
+ * i + j = R + 1 lies just outside the triangle (b0 = -1 / R): a real sample of the triangle's plane, which a bilinear footprint in
+ * a cell on the hypotenuse reads.  Sample number m = j (R + 2) - j (j - 1) / 2 + i; global sample q = t n_tex + m; K = T n_tex,
+ * at most 2^30 per call.
+ *   Blocks: triangle t lies in block k = t >> 1; nb = Wa / B blocks per row; X0 = (k mod nb) B, Y0 = (k / nb) B.  Wa is a multiple
+ * of 4 with B <= Wa <= 16384; Ha = B ceil(ceil(T / 2) / nb) <= 16384 (mesh_tex_height; 0 for T = 0).  An even t puts sample (i, j)
+ * at texel (X0 + i, Y0 + j), an odd t at (X0 + B - 1 - i, Y0 + B - 1 - j).  The atlas is (Ha, Wa, 3) uint8, rows from the top,
+ * r g b, 4-byte aligned.
+ *   Fill: a block texel (lx, ly) with lx + ly = R + 2 belongs to nobody and takes the even triangle's sample (lx - 1, ly) for
+ * lx >= 1, else (0, ly - 1).  Zero are: the odd half (lx + ly >= R + 3) of a last block without an odd triangle, blocks with
+ * 2 k >= T, and the columns >= nb B.  Every byte of the atlas is written exactly once.
+ *
+ * mesh_tex_samples: n_tex (0 for R out of range).  mesh_tex_height: Ha (0 for an argument out of range or Ha > 16384).
+ *
+ * mesh_tex_points: one thread per sample -> points (K,3) fp32: p_a = (v0_a + b1 e1_a) + b2 e2_a in fp32 with b1 = (float)i /
+ * (float)R (IEEE division), e = v - v0, every operation separately rounded; normals_or_null (K,3) fp64, 8-byte aligned: the fp64
+ * cross product of the fp32 edges, (y1 z2 - z1 y2, z1 x2 - x1 z2, x1 y2 - y1 x2), over its length sqrt((nx nx + ny ny) + nz nz),
+ * (0, 0, 1) where that length is zero or not finite.  A BAD triangle (mesh_cast's rule: an index outside [0, V) or a non-finite
+ * coordinate) gives the point (0, 0, 0) and the normal (0, 0, 1); mesh_cast never hits it, so its texels are never shown.
+ *
+ * mesh_tex_atlas: colors (K,3) uint8, one per sample -> atlas.  A gather: one thread per 4 consecutive texels of a row, which
+ * writes its 12 bytes as three 32-bit stores.
+ *
+ * mesh_shade_tex: the hits (tri, b1, b2 of mesh_cast) -> rgb (n,3).  `background` by mesh_shade's rules: tri < 0, tri >= T, or a
+ * triangle naming a vertex outside [0, V).  fx = clamp(b1 R, 0, R) (0 for a NaN), fy likewise from b2.  filter 1, bilinear:
+ * i = min((int)fx, R), fu = fx - i, j and fv likewise; the texels (i, j), (i + 1, j), (i, j + 1), (i + 1, j + 1) of the triangle
+ * as c = byte / 255.0f; rgb = ((1 - fu)(1 - fv) c00 + fu (1 - fv) c10) + ((1 - fu) fv c01 + fu fv c11), times mesh_shade's
+ * ambient + (1 - ambient) |n . d| / (|n| |d|).  filter 0, nearest: the texel ((int)(fx + 0.5f), (int)(fy + 0.5f)).  Whatever b1
+ * and b2 are, every texel read has 0 <= i, j <= R + 1 and so lies in the triangle's own block; for a point of the triangle all
+ * that carry weight are the triangle's own samples.
+ *
+ * NERFHIP_E_BADARG before anything is launched or dereferenced: R, Wa, Ha, T, V, K or n out of range, Wa no multiple of 4 or
+ * below B, Ha not as stated, a null array that would be read or written, an unknown filter, ambient outside [0, 1], a non-finite
+ * background.  NERFHIP_E_ALIGN: normals not 8-byte, any other fp32 / int32 array or the atlas not 4-byte aligned.  n == 0 and
+ * T == 0 are success.                                                                                                           */
+int nerfhip_mesh_tex_samples(int R);
+int nerfhip_mesh_tex_height(int64_t T, int R, int Wa);
+int nerfhip_mesh_tex_points(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, int R, float* points,
+                            double* normals_or_null, nerfhip_stream_t stream);
+int nerfhip_mesh_tex_points_host(const float* vertices, int64_t V, const int32_t* triangles, int64_t T, int R, float* points,
+                                 double* normals_or_null);
+int nerfhip_mesh_tex_atlas(const uint8_t* colors, int64_t T, int R, int Wa, int Ha, uint8_t* atlas, nerfhip_stream_t stream);
+int nerfhip_mesh_tex_atlas_host(const uint8_t* colors, int64_t T, int R, int Wa, int Ha, uint8_t* atlas);
+int nerfhip_mesh_shade_tex(const float* rays, int64_t n, const int32_t* tri, const float* b1, const float* b2, const float* vertices,
+                           int64_t V, const int32_t* triangles, int64_t T, const uint8_t* atlas, int R, int Wa, int Ha, int filter,
+                           float ambient, float background, float* rgb, nerfhip_stream_t stream);
+int nerfhip_mesh_shade_tex_host(const float* rays, int64_t n, const int32_t* tri, const float* b1, const float* b2,
+                                const float* vertices, int64_t V, const int32_t* triangles, int64_t T, const uint8_t* atlas, int R,
+                                int Wa, int Ha, int filter, float ambient, float background, float* rgb);
+
 #ifdef __cplusplus
 }
 #endif

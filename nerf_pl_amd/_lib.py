@@ -212,6 +212,19 @@ for _name, _args in _DECIMATE.items():
     SIGNATURES["nerfhip_mesh_decimate_" + _name] = _args + [_c_void_p]
     SIGNATURES["nerfhip_mesh_decimate_%s_host" % _name] = list(_args)
 
+# mesh texturing (csrc/texture.hip): likewise
+_TEXTURE = {
+    "mesh_tex_points": [_c_void_p, _i64, _c_void_p, _i64, _int, _c_void_p, _c_void_p],
+    "mesh_tex_atlas": [_c_void_p, _i64, _int, _int, _int, _c_void_p],
+    "mesh_shade_tex": [_c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _c_void_p, _int, _int, _int,
+                       _int, _f32, _f32, _c_void_p],
+}
+for _name, _args in _TEXTURE.items():
+    SIGNATURES["nerfhip_" + _name] = _args + [_c_void_p]
+    SIGNATURES["nerfhip_%s_host" % _name] = list(_args)
+SIGNATURES["nerfhip_mesh_tex_samples"] = [_int]
+SIGNATURES["nerfhip_mesh_tex_height"] = [_i64, _int, _int]
+
 
 class AdamFused(ctypes.Structure):
     """include/nerfhip.h: nerfhip_adam_fused"""

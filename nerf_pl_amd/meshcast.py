@@ -7,11 +7,11 @@ deliverable, "mixed reality" — a virtual object inside a NeRF render, z-ordere
 
 Opt-in, and beside everything else: nothing of training, rendering or extraction changes.  The hierarchy's build, the cast, the
 shading and the compositing are HIP kernels (csrc/meshcast.hip); every renderer here obeys the contract of the others:
-rays (n, 8) -> {'rgb_fine', 'depth_fine', 'opacity_fine'}.  The mesh is in world space (no NDC rays), has vertex colours or none
-(no textures), and is static (a moved mesh is built again).
+rays (n, 8) -> {'rgb_fine', 'depth_fine', 'opacity_fine'}.  The mesh is in world space (no NDC rays), has vertex colours, a texture
+(texture.py: a per-triangle atlas) or neither, and is static (a moved mesh is built again).
 
     python -m nerf_pl_amd.meshcast --ply lego.ply --dataset_name blender --root_dir data/nerf_synthetic/lego --split test \\
-        --img_wh 400 400 --out results/mesh --gif lego_mesh.gif
+        --img_wh 400 400 --out results/mesh --gif lego_mesh.gif                 # or --obj lego.obj, a file of texture.write_obj
 """
 import numpy as np
 import torch
@@ -41,14 +41,25 @@ class MeshBVH:
     `triangles` (T, 3) int32, `colors` (V, 3) uint8 or None, and `tris`, `boxes`, `order` of ops.mesh_bvh_build.  The arguments
     are device tensors, or the numpy arrays mesh.extract_color_mesh and mesh.read_ply return (copied to `device`, the current GPU
     unless given).  A triangle with an index outside [0, V) or a non-finite coordinate stays in `triangles` and is never hit;
-    `n_bad` counts them."""
+    `n_bad` counts them.  `texture` is a texture.TextureAtlas of exactly these triangles (its data is copied to the device if it
+    is numpy): `shade` then reads it, through `filter` "bilinear" or "nearest", instead of the vertex colours."""
 
-    def __init__(self, vertices, triangles, colors=None, device=None):
+    def __init__(self, vertices, triangles, colors=None, device=None, texture=None, filter="bilinear"):
         self.vertices = _to_device("vertices", vertices, torch.float32, device)
         self.triangles = _to_device("triangles", triangles, torch.int32, device)
         self.colors = _to_device("colors", colors, torch.uint8, device)
         if self.colors is not None and tuple(self.colors.shape) != tuple(self.vertices.shape):
             raise ValueError("MeshBVH: colors must be (V, 3) like vertices, got %s" % (tuple(self.colors.shape),))
+        if filter not in ops.TEX_FILTERS:
+            raise ValueError("MeshBVH: filter must be 'nearest' or 'bilinear', got %r" % (filter,))
+        self.texture, self.filter = None, filter
+        if texture is not None:
+            if texture.n_triangles != self.triangles.shape[0]:
+                raise ValueError("MeshBVH: the texture is of %d triangles, the mesh has %d (an atlas belongs to one triangle numbering)"
+                                 % (texture.n_triangles, self.triangles.shape[0]))
+            from .texture import TextureAtlas
+            self.texture = TextureAtlas(_to_device("texture", texture.data, torch.uint8, self.vertices.device), texture.res,
+                                        texture.n_triangles)
         self.tris, self.boxes, self.order, self._n_bad = ops.mesh_bvh_build(self.vertices, self.triangles)
 
     @classmethod
@@ -57,13 +68,22 @@ class MeshBVH:
         from .mesh import read_ply
         return cls(*read_ply(path), device=device)
 
+    @classmethod
+    def from_obj(cls, path, device=None, filter="bilinear", res=None):
+        """An OBJ file written by texture.write_obj, with its texture."""
+        from .texture import read_obj
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        vertices, triangles, atlas, _ = read_obj(path, res=res, device=dev)
+        return cls(vertices, triangles, device=device, texture=atlas, filter=filter)
+
     @property
     def n_bad(self):
         """Bad triangles of the mesh (one host read)."""
         return int(self._n_bad.item())
 
     def decimated(self, cell, placement="mean"):
-        """A new MeshBVH of this mesh clustered into cells of edge `cell` (decimate.py), colours included."""
+        """A new MeshBVH of this mesh clustered into cells of edge `cell` (decimate.py), colours included — and WITHOUT the
+        texture: an atlas is tied to the triangle numbering, which decimation changes.  Bake (texture.bake) after decimating."""
         from .decimate import decimate
         return MeshBVH(*decimate(self.vertices, self.triangles, self.colors, cell=cell, placement=placement))
 
@@ -72,14 +92,17 @@ class MeshBVH:
         return ops.mesh_cast(rays, self.tris, self.boxes)
 
     def shade(self, rays, tri, b1, b2, ambient=1.0, background=0.0):
+        if self.texture is not None:
+            return ops.mesh_shade_tex(rays, tri, b1, b2, self.vertices, self.triangles, self.texture.data, self.texture.res, self.filter,
+                                      ambient, background)
         return ops.mesh_shade(rays, tri, b1, b2, self.vertices, self.triangles, self.colors, ambient, background)
 
 
 class MeshRenderer:
     """A callable rays (n, 8) -> {'rgb_fine' (n, 3), 'depth_fine' (n,), 'opacity_fine' (n,)} that casts `bvh`: the vertex colours
-    blended over the hit triangle times ambient + (1 - ambient) |n . d|, depth = the hit's t, opacity 1; a miss is the background
-    (1.0 with white_back, else 0.0), depth 0, opacity 0.  Usable as `inference.evaluate(dataset, MeshRenderer(...))` and inside
-    `occupancy.CulledRenderer`.  ambient = 1 shows the fused colours as they are, which is what a PSNR wants."""
+    blended over the hit triangle (or the texture of a textured `bvh` at the hit) times ambient + (1 - ambient) |n . d|, depth =
+    the hit's t, opacity 1; a miss is the background (1.0 with white_back, else 0.0), depth 0, opacity 0.  Usable as
+    `inference.evaluate(dataset, MeshRenderer(...))` and inside `occupancy.CulledRenderer`.  ambient = 1 shows the fused colours as they are, which is what a PSNR wants."""
 
     def __init__(self, bvh, white_back, ambient=1.0):
         if not 0.0 <= float(ambient) <= 1.0:
@@ -146,7 +169,10 @@ class MixedRenderer:
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="Render the poses of a dataset split from a PLY mesh (no network involved)")
-    ap.add_argument("--ply", required=True, help="the mesh (python -m nerf_pl_amd.mesh, or any file of mesh.write_ply)")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--ply", help="the mesh (python -m nerf_pl_amd.mesh, or any file of mesh.write_ply)")
+    src.add_argument("--obj", help="a textured mesh (python -m nerf_pl_amd.texture, or any file of texture.write_obj)")
+    ap.add_argument("--filter", default="bilinear", choices=["nearest", "bilinear"], help="how --obj's texture is sampled")
     ap.add_argument("--dataset_name", default="blender", choices=["blender", "llff"])
     ap.add_argument("--root_dir", required=True)
     ap.add_argument("--split", default="test")
@@ -162,10 +188,10 @@ def main(argv=None):
     else:
         from .datasets.llff import LLFFDataset
         dataset = LLFFDataset(a.root_dir, split=a.split, img_wh=tuple(a.img_wh))
-    bvh = MeshBVH.from_ply(a.ply)
+    bvh = MeshBVH.from_ply(a.ply) if a.ply else MeshBVH.from_obj(a.obj, filter=a.filter)
     white = getattr(dataset, "white_back", a.dataset_name == "blender")
     out = evaluate(dataset, MeshRenderer(bvh, white_back=white, ambient=a.ambient), dir_name=a.out, gif_path=a.gif)
-    print("%d frames from %s (%d triangles, %d of them bad, %d boxes)" % (len(out["images"]), a.ply, bvh.triangles.shape[0], bvh.n_bad,
+    print("%d frames from %s (%d triangles, %d of them bad, %d boxes)" % (len(out["images"]), a.ply or a.obj, bvh.triangles.shape[0], bvh.n_bad,
                                                                           bvh.boxes.shape[0]))
     if out["mean_psnr"] is not None:
         print("mean PSNR %.2f dB, mean SSIM %.4f against the split's images" % (out["mean_psnr"], out["mean_ssim"]))

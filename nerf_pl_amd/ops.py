@@ -2119,6 +2119,127 @@ def mixed_compose_host(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, 
     return _mixed_compose(_HostArrays, mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background)
 
 
+# ---- texturing a triangle mesh (csrc/texture.hip) ----------------------------------------------------------------
+TEX_MAX_RES = 64
+TEX_MAX_SIDE = 16384
+TEX_MAX_SAMPLES = 1 << 30
+TEX_FILTERS = {"nearest": 0, "bilinear": 1}
+
+
+def mesh_tex_samples(res):
+    """nerfhip_mesh_tex_samples: the samples of one triangle at `res` texel intervals per leg, (res + 2)(res + 3) / 2."""
+    res = int(res)
+    if not 1 <= res <= TEX_MAX_RES:
+        raise ValueError("mesh_tex_samples: res must be in [1, %d], got %d" % (TEX_MAX_RES, res))
+    return (res + 2) * (res + 3) // 2
+
+
+def mesh_tex_height(n_triangles, res, width):
+    """nerfhip_mesh_tex_height: the rows of the atlas of `n_triangles` triangles that is `width` texels wide (include/nerfhip.h)."""
+    T, res, width = int(n_triangles), int(res), int(width)
+    mesh_tex_samples(res)
+    B = res + 3
+    if not 0 <= T <= MESH_MAX_TRIANGLES:
+        raise ValueError("mesh_tex_height: at most 2^28 triangles, got %d" % T)
+    if width % 4 or not B <= width <= TEX_MAX_SIDE:
+        raise ValueError("mesh_tex_height: width must be a multiple of 4 in [%d, %d], got %d" % (B, TEX_MAX_SIDE, width))
+    nb = width // B
+    height = B * -(-((T + 1) // 2) // nb)
+    if height > TEX_MAX_SIDE:
+        raise ValueError("mesh_tex_height: %d triangles at res %d and width %d need %d rows, more than %d"
+                         % (T, res, width, height, TEX_MAX_SIDE))
+    return height
+
+
+def _mesh_tex_points(B, vertices, triangles, res, normals):
+    what = "mesh_tex_points" + B.suffix
+    vertices, triangles = _mesh_arrays(B, what, vertices, triangles)
+    T, K = triangles.shape[0], triangles.shape[0] * mesh_tex_samples(res)
+    if K > TEX_MAX_SAMPLES:
+        raise ValueError("%s: at most 2^30 samples per call, got %d" % (what, K))
+    points = B.empty(vertices, (K, 3), "float32")
+    nrm = B.empty(vertices, (K, 3), "float64") if normals else None
+    B.call("nerfhip_mesh_tex_points", B.ptr(vertices), vertices.shape[0], B.ptr(triangles), T, int(res), B.ptr(points), B.ptr(nrm))
+    return points, nrm
+
+
+@device_guard
+def mesh_tex_points(vertices, triangles, res, normals=True):
+    """nerfhip_mesh_tex_points: vertices (V, 3) fp32 and triangles (T, 3) int32 on the device -> (points (K, 3) fp32, normals (K, 3)
+    fp64 or None), K = T mesh_tex_samples(res): the point of every sample of the atlas on its triangle's plane, and its triangle's
+    unit normal.  A bad triangle (mesh_bvh_build's rule) gives (0, 0, 0) and (0, 0, 1)."""
+    return _mesh_tex_points(_DeviceArrays, vertices, triangles, res, normals)
+
+
+def mesh_tex_points_host(vertices, triangles, res, normals=True):
+    """nerfhip_mesh_tex_points_host (host, no GPU): numpy in, numpy (points, normals or None) out."""
+    return _mesh_tex_points(_HostArrays, vertices, triangles, res, normals)
+
+
+def _mesh_tex_atlas(B, colors, n_triangles, res, width):
+    what = "mesh_tex_atlas" + B.suffix
+    colors = B.array(what, "colors", colors, "uint8", (3,))
+    T, height = int(n_triangles), mesh_tex_height(n_triangles, res, width)
+    if colors.shape[0] != T * mesh_tex_samples(res):
+        raise ValueError("%s: %d triangles at res %d have %d samples, got %d colours"
+                         % (what, T, res, T * mesh_tex_samples(res), colors.shape[0]))
+    atlas = B.empty(colors, (height, int(width), 3), "uint8")
+    B.call("nerfhip_mesh_tex_atlas", B.ptr(colors), T, int(res), int(width), height, B.ptr(atlas))
+    return atlas
+
+
+@device_guard
+def mesh_tex_atlas(colors, n_triangles, res, width):
+    """nerfhip_mesh_tex_atlas: colors (K, 3) uint8 on the device, one per sample in `mesh_tex_points`' order -> the atlas
+    (mesh_tex_height(n_triangles, res, width), width, 3) uint8 in the layout of include/nerfhip.h, every byte written."""
+    return _mesh_tex_atlas(_DeviceArrays, colors, n_triangles, res, width)
+
+
+def mesh_tex_atlas_host(colors, n_triangles, res, width):
+    """nerfhip_mesh_tex_atlas_host (host, no GPU): numpy in, numpy atlas out."""
+    return _mesh_tex_atlas(_HostArrays, colors, n_triangles, res, width)
+
+
+def _mesh_shade_tex(B, rays, tri, b1, b2, vertices, triangles, atlas, res, filter, ambient, background):
+    what = "mesh_shade_tex" + B.suffix
+    if filter not in TEX_FILTERS:
+        raise ValueError("%s: filter must be 'nearest' or 'bilinear', got %r" % (what, filter))
+    rays = B.array(what, "rays", rays, "float32", (8,))
+    tri, b1, b2 = B.array(what, "tri", tri, "int32", ()), B.array(what, "b1", b1, "float32", ()), B.array(what, "b2", b2, "float32", ())
+    vertices, triangles = _mesh_arrays(B, what, vertices, triangles)
+    atlas = B.array(what, "atlas", atlas, "uint8")
+    if atlas.ndim != 3 or atlas.shape[2] != 3:
+        raise ValueError("%s: atlas must be (height, width, 3), got %s" % (what, tuple(atlas.shape)))
+    T, height, width = triangles.shape[0], atlas.shape[0], atlas.shape[1]
+    if height != mesh_tex_height(T, res, width):
+        raise ValueError("%s: the atlas of %d triangles at res %d and width %d has %d rows, got %d"
+                         % (what, T, res, width, mesh_tex_height(T, res, width), height))
+    n = rays.shape[0]
+    if not tri.shape[0] == b1.shape[0] == b2.shape[0] == n:
+        raise ValueError("%s: tri, b1 and b2 must have one entry per ray" % what)
+    B.same_device(what, rays, tri, b1, b2, vertices, triangles, atlas)
+    ambient, background = float(ambient), float(background)
+    if not 0.0 <= ambient <= 1.0:
+        raise ValueError("%s: ambient must be in [0, 1], got %r" % (what, ambient))
+    rgb = B.empty(rays, (n, 3), "float32")
+    B.call("nerfhip_mesh_shade_tex", B.ptr(rays), n, B.ptr(tri), B.ptr(b1), B.ptr(b2), B.ptr(vertices), vertices.shape[0],
+           B.ptr(triangles), T, B.ptr(atlas), int(res), width, height, TEX_FILTERS[filter], ambient, background, B.ptr(rgb))
+    return rgb
+
+
+@device_guard
+def mesh_shade_tex(rays, tri, b1, b2, vertices, triangles, atlas, res, filter="bilinear", ambient=1.0, background=0.0):
+    """nerfhip_mesh_shade_tex: the hits of `mesh_cast` -> rgb (n, 3): the hit triangle's patch of `atlas` ((height, width, 3) uint8
+    of `mesh_tex_atlas` at `res`) at (b1, b2), the nearest texel or the bilinear blend of the four around it, times `mesh_shade`'s
+    ambient term; `background` for a miss."""
+    return _mesh_shade_tex(_DeviceArrays, rays, tri, b1, b2, vertices, triangles, atlas, res, filter, ambient, background)
+
+
+def mesh_shade_tex_host(rays, tri, b1, b2, vertices, triangles, atlas, res, filter="bilinear", ambient=1.0, background=0.0):
+    """nerfhip_mesh_shade_tex_host (host, no GPU): numpy in, numpy rgb (n, 3) out."""
+    return _mesh_shade_tex(_HostArrays, rays, tri, b1, b2, vertices, triangles, atlas, res, filter, ambient, background)
+
+
 # ---- mesh decimation (csrc/decimate.hip, DESIGN.md §22) -----------------------------------------------------------------------
 DECIMATE_MAX_ITEMS = 1 << 28
 DECIMATE_PLACEMENTS = {"mean": 0, "quadric": 1}

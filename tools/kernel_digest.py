@@ -9,6 +9,7 @@
     python tools/kernel_digest.py baked                          # the baked-volume build and march kernels
     python tools/kernel_digest.py meshcast                       # the mesh hierarchy's build, the cast, shade and compose
     python tools/kernel_digest.py decimate                       # the mesh decimation's kernels
+    python tools/kernel_digest.py texture                        # the texture atlas' points, gather and lookup
     python tools/kernel_digest.py --against old.txt > both.txt   # side by side with an earlier output, differences marked
 
 The jobs are nerf_pl_amd.build._jobs() — the same sources, flags and per-file -mllvm options as the library build (with
