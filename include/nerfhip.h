@@ -1002,6 +1002,61 @@ int nerfhip_mixed_compose_host(int mode, int64_t n, const float* rgb_n, const fl
                                const int32_t* tri, const float* t, const float* rgb_m, float tau, float background, float* rgb,
                                float* depth, float* opacity, uint8_t* mask_or_null);
 
+/* ---- shadows for mixed renders: any-hit mesh rays, light samples, lit compose  (the reference README's showpiece: the inserted
+ *      object "casts shadow on the scene") -------------------------------------------------------------------------
+ * Opt-in and beside everything else.  csrc/shadow_core.h states every routine exactly, and every entry point has a _host twin (a
+ * HOST function: host pointers, no GPU, the same routine in a loop, the same bits: plain fp32, IEEE division and square root, no
+ * libm).  Nothing is allocated, nothing synchronises, launches go to the caller's stream.  1 <= K <= 64 samples per pixel,
+ * n K <= 2^30 rows.
+ *
+ * mesh_occluded: rays, tris, boxes, T as mesh_cast reads them -> hit (n) uint8: 1 iff some good triangle is accepted by
+ * mesh_cast's triangle test with near <= t <= far, that is iff mesh_cast would return tri >= 0.  The same ray set-up, triangle
+ * test, box test (limit = far) and bounded pre-order walk, left at the first accepted triangle; no t, no barycentrics, no tie
+ * rule.  The answer belongs to the mesh and the row, not to the traversal: the hierarchy, brute force (mesh_occluded_host with
+ * brute != 0, which ignores `boxes`) and mesh_cast agree in every bit.
+ *
+ * shadow_rays: primary rows rays (n,8), 16-byte aligned, and the surface distance s (n) of each -> rows (n K, 8), 16-byte
+ * aligned, sample k of pixel i at row i K + k, and cosine_or_null (n).  p = o + s d.  The light: kind 0 directional, (lx, ly, lz)
+ * the direction TOWARDS the light (any non-zero length); kind 1 point, (lx, ly, lz) its position.  A row is [p, d_k, bias, far]:
+ * d_k the unit vector towards light sample k, far = reach (directional) or |L_k - p| (point).  A pixel has ZERO ROWS (all eight
+ * values +0) when s is not finite or <= 0, when its primary row or p holds a non-finite value, or when p lies on a point light;
+ * a single sample that coincides with p gives one zero row.  mesh_cast and mesh_occluded miss a zero row, baked_render returns
+ * opacity 0 for it.  The light is a square of half-width `radius` facing the pixel, with the frame e1 = normalise(c x axis),
+ * e2 = c x e1, c the unit direction to the light's centre and axis the coordinate axis of its smallest |component| (x, y, z on
+ * ties).  Sample k is offset by radius (u_k e1 + v_k e2): d_k = normalise(c + offset) (directional), L_k = L + offset (point).
+ * (u_k, v_k) in [-1, 1)^2 is the R2 sequence in 32-bit integers, x_k = 2^31 + k 3242174889, y_k = 2^31 + k 2447445414 (mod
+ * 2^32), u = (x >> 8) 2^-23 - 1; rotate = 1 adds h = hash(i) to x and hash(h ^ 0x9e3779b9) to y (csrc/shadow_core.h states the
+ * hash); rotate = 0 uses one sequence for every pixel.  radius == 0 skips the offset: the K rows of a pixel are its K = 1 row in
+ * every bit.  cosine: 1 everywhere when tri_or_null is null, and where tri < 0; elsewhere max(n . c, 0) clamped to 1, n the unit
+ * geometric normal of triangle tri[i] of (vertices, V, triangles, T) as mesh_shade forms it, turned to the camera (n . d <= 0);
+ * 0 for a pixel with zero rows, a tri >= T, a triangle naming a vertex outside [0, V), a normal of zero or non-finite length.
+ *
+ * light_compose: rgb (n,3), mask (n) uint8 (mixed_compose's: 1 on a mesh pixel), cosine (n), hit (n K) uint8 of mesh_occluded,
+ * trans_or_null (n K): the scene's transmittance along each row (null: 1) -> rgb_out (n,3), visibility_or_null (n): the V
+ * applied.  Mesh pixel: V = (sum_k (hit_k ? 0 : 1) trans_k) / K, rgb_out = rgb (ambient + ((1 - ambient) cosine) V).  Scene
+ * pixel: V = (sum_k (hit_k ? 0 : 1)) / K (trans is not read), rgb_out = rgb (1 - strength (1 - V)).  Sums in k order.
+ * ambient = 1 and strength = 0 make both factors an exact 1.
+ *
+ * NERFHIP_E_BADARG before anything is launched or dereferenced: n, T, V or K out of range, n K > 2^30, an unknown kind, rotate
+ * not 0 or 1, bias or reach not finite and > 0, radius not finite and >= 0, a non-finite light, a directional light of zero
+ * length, ambient or strength outside [0, 1], a null pointer that n > 0 would read or write.  NERFHIP_E_ALIGN for rays, rows or
+ * tris not 16-byte aligned, any other float or int32 array not 4-byte aligned.  n == 0 is success.                              */
+int nerfhip_mesh_occluded(const float* rays, int64_t n, const float* tris, const float* boxes, int64_t T, uint8_t* hit,
+                          nerfhip_stream_t stream);
+int nerfhip_mesh_occluded_host(const float* rays, int64_t n, const float* tris, const float* boxes, int64_t T, int brute, uint8_t* hit);
+int nerfhip_shadow_rays(const float* rays, const float* s, int64_t n, const int32_t* tri_or_null, const float* vertices, int64_t V,
+                        const int32_t* triangles, int64_t T, int kind, float lx, float ly, float lz, float bias, float reach, int K,
+                        float radius, int rotate, float* rows, float* cosine_or_null, nerfhip_stream_t stream);
+int nerfhip_shadow_rays_host(const float* rays, const float* s, int64_t n, const int32_t* tri_or_null, const float* vertices, int64_t V,
+                             const int32_t* triangles, int64_t T, int kind, float lx, float ly, float lz, float bias, float reach,
+                             int K, float radius, int rotate, float* rows, float* cosine_or_null);
+int nerfhip_light_compose(int64_t n, const float* rgb, const uint8_t* mask, const float* cosine, const uint8_t* hit,
+                          const float* trans_or_null, int K, float ambient, float strength, float* rgb_out,
+                          float* visibility_or_null, nerfhip_stream_t stream);
+int nerfhip_light_compose_host(int64_t n, const float* rgb, const uint8_t* mask, const float* cosine, const uint8_t* hit,
+                               const float* trans_or_null, int K, float ambient, float strength, float* rgb_out,
+                               float* visibility_or_null);
+
 /* ---- mesh decimation: grid vertex clustering with mean or quadric placement  (no counterpart in the reference, whose answer to a
  *      9.4 M triangle mesh is a coarser sigma grid) ----------------------------------------------------------------
  * Opt-in and beside everything else.  csrc/decimate_core.h states every routine exactly, and every entry point has a _host twin

@@ -225,6 +225,18 @@ for _name, _args in _TEXTURE.items():
 SIGNATURES["nerfhip_mesh_tex_samples"] = [_int]
 SIGNATURES["nerfhip_mesh_tex_height"] = [_i64, _int, _int]
 
+# shadows for mixed renders (csrc/shadow.hip): likewise; mesh_occluded's _host twin takes `brute` as mesh_cast's does
+_SHADOW = {
+    "shadow_rays": [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _i64, _int, _f32, _f32, _f32, _f32, _f32, _int,
+                    _f32, _int, _c_void_p, _c_void_p],
+    "light_compose": [_i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _int, _f32, _f32, _c_void_p, _c_void_p],
+}
+for _name, _args in _SHADOW.items():
+    SIGNATURES["nerfhip_" + _name] = _args + [_c_void_p]
+    SIGNATURES["nerfhip_%s_host" % _name] = list(_args)
+SIGNATURES["nerfhip_mesh_occluded"] = [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p]
+SIGNATURES["nerfhip_mesh_occluded_host"] = [_c_void_p, _i64, _c_void_p, _c_void_p, _i64, _int, _c_void_p]
+
 
 class AdamFused(ctypes.Structure):
     """include/nerfhip.h: nerfhip_adam_fused"""

@@ -2119,6 +2119,150 @@ def mixed_compose_host(mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau=0.5, 
     return _mixed_compose(_HostArrays, mode, rgb_n, depth_n, opacity_n, tri, t, rgb_m, tau, background)
 
 
+# ---- shadows for mixed renders (csrc/shadow.hip) -----------------------------------------------------------------
+LIGHT_KINDS = {"directional": 0, "point": 1}
+SHADOW_MAX_SAMPLES = 64
+
+
+def _mesh_occluded(B, rays, tris, boxes, brute=False):
+    what = "mesh_occluded" + B.suffix
+    rays = B.array(what, "rays", rays, "float32", (8,))
+    tris = B.array(what, "tris", tris, "float32", (12,))
+    T = tris.shape[0]
+    boxes = None if brute else B.array(what, "boxes", boxes, "float32", (6,))
+    if boxes is not None and boxes.shape[0] != mesh_bvh_nodes(T):
+        raise ValueError("%s: a hierarchy of %d triangles has %d boxes, got %d" % (what, T, mesh_bvh_nodes(T), boxes.shape[0]))
+    B.same_device(what, rays, tris, boxes)
+    n = rays.shape[0]
+    hit = B.empty(rays, n, "uint8")
+    only_host = (int(bool(brute)),) if B is _HostArrays else ()
+    B.call("nerfhip_mesh_occluded", B.ptr(rays), n, B.ptr(tris), B.ptr(boxes), T, *only_host, B.ptr(hit))
+    return hit
+
+
+@device_guard
+def mesh_occluded(rays, tris, boxes):
+    """nerfhip_mesh_occluded: rays (n, 8) fp32 against the hierarchy of `mesh_bvh_build` -> hit (n,) uint8 on the device: 1 iff
+    `mesh_cast` would return tri >= 0, found by leaving the walk at the first accepted triangle."""
+    return _mesh_occluded(_DeviceArrays, rays, tris, boxes)
+
+
+def mesh_occluded_host(rays, tris, boxes, brute=False):
+    """nerfhip_mesh_occluded_host (host, no GPU): numpy in, numpy hit (n,) uint8 out.  brute=True tests every triangle and reads no
+    box (boxes may be None)."""
+    return _mesh_occluded(_HostArrays, rays, tris, boxes, brute)
+
+
+def _samples_arg(what, samples):
+    K = int(samples)
+    if K != samples or not 1 <= K <= SHADOW_MAX_SAMPLES:
+        raise ValueError("%s: samples must be an integer in [1, %d], got %r" % (what, SHADOW_MAX_SAMPLES, samples))
+    return K
+
+
+def _shadow_rays(B, rays, s, kind, light, bias, reach, samples, radius, rotate, tri, vertices, triangles, cosine):
+    import math
+    what = "shadow_rays" + B.suffix
+    if kind not in LIGHT_KINDS:
+        raise ValueError("%s: kind must be 'directional' or 'point', got %r" % (what, kind))
+    light = [float(v) for v in light]
+    if len(light) != 3 or not all(math.isfinite(v) for v in light):
+        raise ValueError("%s: the light must be three finite numbers, got %r" % (what, light))
+    if kind == "directional" and not any(light):
+        raise ValueError("%s: a directional light needs a non-zero direction" % what)
+    K = _samples_arg(what, samples)
+    bias, reach, radius = float(bias), float(reach), float(radius)
+    if not (bias > 0.0 and math.isfinite(bias)):
+        raise ValueError("%s: bias must be finite and > 0, got %r" % (what, bias))
+    if not (reach > 0.0 and math.isfinite(reach)):
+        raise ValueError("%s: reach must be finite and > 0, got %r" % (what, reach))
+    if not (radius >= 0.0 and math.isfinite(radius)):
+        raise ValueError("%s: radius must be finite and >= 0, got %r" % (what, radius))
+    rays = B.array(what, "rays", rays, "float32", (8,))
+    s = B.array(what, "s", s, "float32", ())
+    n = rays.shape[0]
+    if s.shape[0] != n:
+        raise ValueError("%s: s must have one entry per ray, got %d for %d rays" % (what, s.shape[0], n))
+    if n * K > 1 << 30:
+        raise ValueError("%s: at most 2^30 rows per call, got %d x %d" % (what, n, K))
+    V = T = 0
+    if tri is not None:
+        if vertices is None or triangles is None:
+            raise ValueError("%s: tri needs the mesh's vertices and triangles" % what)
+        tri = B.array(what, "tri", tri, "int32", ())
+        if tri.shape[0] != n:
+            raise ValueError("%s: tri must have one entry per ray, got %d for %d rays" % (what, tri.shape[0], n))
+        vertices, triangles = _mesh_arrays(B, what, vertices, triangles)
+        V, T = vertices.shape[0], triangles.shape[0]
+    else:
+        vertices = triangles = None
+    B.same_device(what, rays, s, tri, vertices, triangles)
+    rows = B.empty(rays, (n * K, 8), "float32")
+    cos = B.empty(rays, n, "float32") if cosine else None
+    B.call("nerfhip_shadow_rays", B.ptr(rays), B.ptr(s), n, B.ptr(tri), B.ptr(vertices), V, B.ptr(triangles), T, LIGHT_KINDS[kind],
+           light[0], light[1], light[2], bias, reach, K, radius, int(bool(rotate)), B.ptr(rows), B.ptr(cos))
+    return rows, cos
+
+
+@device_guard
+def shadow_rays(rays, s, kind, light, bias, reach, samples=1, radius=0.0, rotate=True, tri=None, vertices=None, triangles=None,
+                cosine=True):
+    """nerfhip_shadow_rays: primary rays (n, 8) and the surface distance s (n,) of each -> (rows (n samples, 8): sample k of pixel i
+    at row i samples + k, from p = o + s d towards sample k of the light, near = bias, far = reach or the distance to a point
+    light; cosine (n,) or None).  `kind` 'directional' (`light` the direction towards it) or 'point' (`light` its position);
+    the light is a square of half-width `radius`.  A pixel without a surface (s not finite or <= 0) gets zero rows, which hit
+    nothing.  `tri` (n,) int32 with `vertices`, `triangles`: the mesh layer's hit, for cosine = max(n . l, 0); -1 or no `tri`: 1."""
+    return _shadow_rays(_DeviceArrays, rays, s, kind, light, bias, reach, samples, radius, rotate, tri, vertices, triangles, cosine)
+
+
+def shadow_rays_host(rays, s, kind, light, bias, reach, samples=1, radius=0.0, rotate=True, tri=None, vertices=None, triangles=None,
+                     cosine=True):
+    """nerfhip_shadow_rays_host (host, no GPU): numpy in, numpy (rows, cosine or None) out."""
+    return _shadow_rays(_HostArrays, rays, s, kind, light, bias, reach, samples, radius, rotate, tri, vertices, triangles, cosine)
+
+
+def _light_compose(B, rgb, mask, cosine, hit, trans, ambient, strength, visibility):
+    what = "light_compose" + B.suffix
+    ambient, strength = float(ambient), float(strength)
+    if not 0.0 <= ambient <= 1.0:
+        raise ValueError("%s: ambient must be in [0, 1], got %r" % (what, ambient))
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError("%s: strength must be in [0, 1], got %r" % (what, strength))
+    rgb = B.array(what, "rgb", rgb, "float32", (3,))
+    mask, hit = B.array(what, "mask", mask, "uint8", ()), B.array(what, "hit", hit, "uint8", ())
+    cosine = B.array(what, "cosine", cosine, "float32", ())
+    n = rgb.shape[0]
+    if not mask.shape[0] == cosine.shape[0] == n:
+        raise ValueError("%s: mask and cosine must have one entry per pixel" % what)
+    K = hit.shape[0] // n if n else 1
+    if hit.shape[0] != (n * K if n else 0) or not 1 <= K <= SHADOW_MAX_SAMPLES:
+        raise ValueError("%s: hit must hold 1 to %d samples for each of the %d pixels, got %d" % (what, SHADOW_MAX_SAMPLES, n, hit.shape[0]))
+    if trans is not None:
+        trans = B.array(what, "trans", trans, "float32", ())
+        if trans.shape[0] != hit.shape[0]:
+            raise ValueError("%s: trans must have one entry per row, got %d for %d rows" % (what, trans.shape[0], hit.shape[0]))
+    B.same_device(what, rgb, mask, cosine, hit, trans)
+    out = B.empty(rgb, (n, 3), "float32")
+    vis = B.empty(rgb, n, "float32") if visibility else None
+    B.call("nerfhip_light_compose", n, B.ptr(rgb), B.ptr(mask), B.ptr(cosine), B.ptr(hit), B.ptr(trans), K, ambient, strength, B.ptr(out),
+           B.ptr(vis))
+    return out, vis
+
+
+@device_guard
+def light_compose(rgb, mask, cosine, hit, trans=None, ambient=0.3, strength=0.7, visibility=True):
+    """nerfhip_light_compose: rgb (n, 3), mask (n,) uint8 of `mixed_compose`, cosine (n,) of `shadow_rays`, hit (n K,) uint8 of
+    `mesh_occluded` on its rows, trans (n K,) or None: the scene's transmittance along each row -> (rgb_out (n, 3), V (n,) or
+    None).  Mesh pixel: V = mean_k((1 - hit) trans), rgb (ambient + (1 - ambient) cosine V); scene pixel: V = mean_k(1 - hit),
+    rgb (1 - strength (1 - V)).  ambient = 1 and strength = 0 pass every bit of rgb through."""
+    return _light_compose(_DeviceArrays, rgb, mask, cosine, hit, trans, ambient, strength, visibility)
+
+
+def light_compose_host(rgb, mask, cosine, hit, trans=None, ambient=0.3, strength=0.7, visibility=True):
+    """nerfhip_light_compose_host (host, no GPU): numpy in, numpy (rgb_out, V or None) out."""
+    return _light_compose(_HostArrays, rgb, mask, cosine, hit, trans, ambient, strength, visibility)
+
+
 # ---- texturing a triangle mesh (csrc/texture.hip, DESIGN.md §23) ----------------------------------------------------------------
 TEX_MAX_RES = 64
 TEX_MAX_SIDE = 16384
