@@ -1,7 +1,9 @@
 """GPU: NeRF shapes other than the reference's default (models/nerf.py:42-81 takes any D / W / skips / channel counts) run layer
 by layer through csrc/linear.hip.  Checked against (1) a plain torch fp32 restatement of one layer, (2) vectors minted from the
 real reference for three non-default configurations (tests/golden/reference_golden_arch.npz), (3) the fused kernels on the
-default shape, (4) the CPU oracle on a deeper default-width network.  Tolerances: exact-fp32 MFMA 1e-4 class, bf16 3e-2 class."""
+default shape, (4) the CPU oracle on a deeper default-width network.  Tolerances: exact-fp32 MFMA 1e-4 class, bf16 3e-2 class.
+These are whole-tensor bounds; the elementwise check of csrc/linear.hip — every entry point against the fp64 sum of the operands it
+multiplies, componentwise bounds, load paths, guards, accumulate, gb == NULL — is tests/test_gpu_linear_exact.py."""
 import os
 
 import numpy as np
